@@ -17,14 +17,26 @@ Scaling is WEAK: each GPU prioritizes its own fixed-size test shard against
 the full (replicated) train-AT set.
 
 Usage: python bench.py --gpus N --steps K --warmup W [--batch B]
+                       [--dump-outputs DIR] [--full]
 (the driver launches N>1 via torch.distributed.run, one rank per GPU).
+
+A plain run does only what the headline figure needs: setup, warm-up, the
+K timed steps, the result line. --dump-outputs DIR additionally writes the
+scores the last timed step returned (DIR/<name>.npy, float32) so two builds
+can be compared output for output: with the same arguments every input
+(weights, train ATs, test batches) is identical from run to run. --full adds
+the auxiliary quality signals (last-batch APFDs and the deep-gini nominal
+APFD pin), which a plain run leaves out of the result line's config (null).
 """
 
 import argparse
+import concurrent.futures
 import json
 import os
 import sys
 import time
+
+_T_START = time.perf_counter()  # log() stamps are seconds since process start
 
 import numpy as np
 import torch
@@ -43,7 +55,8 @@ AT_TAP = ResNet20.sa_layers  # layer 9: 8x8x64 = 4096-wide feature map
 
 def log(rank, msg):
     if rank == 0:
-        print(f"[bench] {msg}", file=sys.stderr, flush=True)
+        print(f"[bench] +{time.perf_counter() - _T_START:5.1f}s {msg}",
+              file=sys.stderr, flush=True)
 
 
 class GraphedExtractor:
@@ -169,6 +182,72 @@ class GraphedExtractor:
         return ats, probs
 
 
+def dump_outputs(out_dir, last):
+    """Write what the last timed step returned to its caller — the deep-gini,
+    DSA and per-class LSA scores and the (remapped) predicted classes of that
+    step's batch — as out_dir/<name>.npy, float32, one value per input."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = ("deep_gini", "dsa", "pc_lsa", "pred")
+    for name, t in zip(names, last):
+        if t is None:
+            continue
+        arr = torch.as_tensor(t).detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr.astype(np.float32))
+
+
+QUALITY_KEYS = (
+    "apfd_gini_lastbatch",
+    "apfd_gini_nominal_lastbatch",
+    "apfd_dsa_lastbatch",
+    "apfd_pclsa_lastbatch",
+)
+
+
+def quality_signals(rank, last, last_labels, batch):
+    """--full only: APFD of each scorer's ordering on the last timed batch,
+    and the deep-gini nominal-half pin. Returns the config entries (None
+    where an APFD is undefined)."""
+    gini, dsa_last, lsa_last, pred = last
+    mis = (pred.cpu().numpy() != last_labels.numpy())
+
+    def _apfd(scores):
+        if not mis.any():
+            return float("nan")
+        return apfd_from_order(
+            mis, np.argsort(-scores.float().cpu().numpy(), kind="stable")
+        )
+
+    apfd = _apfd(gini)
+    apfd_dsa = _apfd(dsa_last)
+    apfd_lsa = _apfd(lsa_last) if lsa_last is not None else float("nan")
+    # quality pin (VERDICT r01 item 3): on the NOMINAL half of the batch a
+    # trained model's deep-gini ordering must beat random — rules out a
+    # sign/negation bug producing a plausible-looking throughput number
+    half = batch // 2
+    mis_nom = mis[:half]
+    apfd_gini_nom = float("nan")
+    if mis_nom.sum() >= 10:
+        apfd_gini_nom = apfd_from_order(
+            mis_nom,
+            np.argsort(-gini[:half].float().cpu().numpy(), kind="stable"),
+        )
+        # assert only on statistically meaningful configs: a large nominal
+        # half and a model that actually learned (tiny smoke configs train
+        # for seconds and gini on a near-random model IS near-random)
+        if half >= 2000 and mis_nom.mean() < 0.5:
+            assert apfd_gini_nom > 0.5, (
+                f"deep-gini nominal APFD {apfd_gini_nom:.3f} <= 0.5: softmax "
+                f"ordering is not ranking real faults"
+            )
+    log(rank, f"last-batch accuracy={1.0 - mis.mean():.3f} "
+              f"apfd_gini={apfd:.3f} apfd_gini_nominal={apfd_gini_nom:.3f} "
+              f"apfd_dsa={apfd_dsa:.3f} apfd_lsa={apfd_lsa:.3f}")
+    values = (apfd, apfd_gini_nom, apfd_dsa, apfd_lsa)
+    return {
+        k: None if np.isnan(v) else v for k, v in zip(QUALITY_KEYS, values)
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -177,12 +256,19 @@ def main():
     ap.add_argument("--batch", type=int, default=20480,
                     help="test inputs per GPU per step (default = the reference's\n                    OOD test-set size; larger batches amortize per-step overhead)")
     ap.add_argument("--train-n", type=int, default=TRAIN_N)
-    ap.add_argument("--setup-epochs", type=int, default=4,
-                    help="untimed warm-up training epochs (class diversity)")
+    ap.add_argument("--setup-epochs", type=int, default=1,
+                    help="untimed warm-up training epochs (class diversity); "
+                         "one epoch is 80 Adam steps of 128 inputs")
     ap.add_argument("--shard-train", action="store_true",
                     help="strong scaling: shard the train-AT axis across "
                          "ranks; every rank scores the SAME batch against "
                          "its shard, partials merge over RCCL")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the scores the last "
+                         "timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also compute the auxiliary quality signals "
+                         "(last-batch APFDs, deep-gini nominal APFD pin)")
     args = ap.parse_args()
 
     rank, world, device = pdist.init_from_env()
@@ -201,42 +287,73 @@ def main():
         raise RuntimeError("bench on GPU requires the _tip_hip extension")
 
     torch.manual_seed(0)  # identical weights on every rank
-    model = ResNet20().to(device).eval()
+    model = ResNet20().eval()  # trained on the host below, then moved
 
     # ---- setup (untimed) ----
     # Brief training on class-structured synthetic data so the model's
     # predictions spread over all classes: a random-init net predicts one
     # class for everything, which would degenerate the per-class DSA/LSA
     # work in the timed region (work-skipping = invalid measurement).
-    from simple_tip_amd.studies.synthetic import synthetic_images
+    from simple_tip_amd.studies.synthetic import corrupt_images, synthetic_images
 
-    tx, ty = synthetic_images("bench_cifar10", "warm", 10240, (3, 32, 32), 10)
+    # Host-side synthetic data. Every array is seeded by its (study, split)
+    # name alone, so generating the splits on worker threads (numpy releases
+    # the GIL) during the warm-up training changes no value, only the setup's
+    # wall time: serially this was about half of a plain run.
+    shard_train = bool(args.shard_train) and world > 1
+    n_pool = min(max(args.steps + args.warmup, 4), 8)
+
+    def gen_split(split, n):
+        return synthetic_images("bench_cifar10", split, n, (3, 32, 32), 10)
+
+    def gen_test_batch(i):
+        # shard-train mode: every rank scores the SAME global batch (strong
+        # scaling), so the pool seed must not depend on rank
+        tag = f"test-shared-{i}" if shard_train else f"test-r{rank}-{i}"
+        px, py = gen_split(tag, args.batch)
+        # reference OOD recipe: half the batch is corrupted, so the model
+        # has real faults for the APFD quality signal
+        half = args.batch // 2
+        px[half:] = corrupt_images("bench_cifar10", px[half:], severity=0.5)
+        return px, py
+
+    datagen = concurrent.futures.ThreadPoolExecutor(max_workers=6)
+    warm_f = datagen.submit(gen_split, "warm", 10240)
+    train_f = datagen.submit(gen_split, "train", args.train_n)
+    pool_f = [datagen.submit(gen_test_batch, i) for i in range(n_pool)]
+    datagen.shutdown(wait=False)
+
+    tx, ty = warm_f.result()
     tx_t = torch.from_numpy(tx)
     ty_t = torch.from_numpy(ty)
     opt = torch.optim.Adam(model.parameters(), lr=2e-3)
     model.train()
+    # The warm-up runs on the host in fp32, whatever the device. On the GPU
+    # it went through MIOpen, whose backward solvers accumulate with atomics
+    # (weights, train ATs and so every score differed from run to run, the
+    # predicted-class histogram by 10x) and whose kernels compile at first
+    # use (~14 s with an empty cache); its deterministic solvers cost 0.2 s
+    # a step on top. An epoch of 80 steps of 128 on the host takes a few
+    # seconds and gives identical weights every run on every build. Keep
+    # the step count: after 20 steps (of 512) the BN running statistics had
+    # not converged and the eval-mode net predicted one or two classes.
+    log(rank, f"warm-up training x{args.setup_epochs} epochs (host)")
     for epoch in range(args.setup_epochs):
         perm = torch.randperm(tx_t.shape[0])
-        for s in range(0, tx_t.shape[0], 512):
-            idx = perm[s : s + 512]
-            xb = tx_t[idx].to(device)
-            yb = ty_t[idx].to(device)
+        for s in range(0, tx_t.shape[0], 128):
+            idx = perm[s : s + 128]
             opt.zero_grad(set_to_none=True)
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=on_gpu):
-                loss = torch.nn.functional.cross_entropy(model(xb).float(), yb)
+            loss = torch.nn.functional.cross_entropy(model(tx_t[idx]), ty_t[idx])
             loss.backward()
             opt.step()
-    model.eval()
+    model.eval().to(device)
     if world > 1:
         # correctness by construction: rank-0 weights everywhere
         for p in model.parameters():
             torch.distributed.broadcast(p.data, src=0)
 
     # train-AT extraction + SA fits (the reference's "setup" bucket)
-    g = torch.Generator().manual_seed(1234)
-    base_x, base_y = synthetic_images(
-        "bench_cifar10", "train", args.train_n, (3, 32, 32), 10
-    )
+    base_x, base_y = train_f.result()
     train_x = torch.from_numpy(base_x)
     # in shard-train mode each rank forwards only its slice of the batch, so
     # the hipGraph is captured at the slice size
@@ -247,7 +364,6 @@ def main():
         cap_batch = args.batch
     extractor = GraphedExtractor(model, cap_batch, device, use_graph=on_gpu)
 
-    shard_train = bool(args.shard_train) and world > 1
     if shard_train:
         # each rank extracts ATs for its row shard, then the full train-AT
         # tensor all-gathers (one-time, untimed setup) so SA fits are
@@ -312,21 +428,12 @@ def main():
     # with a dedicated prefetch stream). TIP_HOST_POOL=1 restores pinned-
     # host batches with double-buffered prefetch for the streaming story.
     host_pool = os.environ.get("TIP_HOST_POOL") == "1"
-    n_pool = min(max(args.steps + args.warmup, 4), 8)
+    log(rank, f"staging {n_pool} test batches")
     pool, labels_pool = [], []
     nhwc_pool = extractor.fused is not None
-    from simple_tip_amd.studies.synthetic import corrupt_images
     for i in range(n_pool):
-        # shard-train mode: every rank scores the SAME global batch (strong
-        # scaling), so the pool seed must not depend on rank
-        tag = f"test-shared-{i}" if shard_train else f"test-r{rank}-{i}"
-        px, py = synthetic_images(
-            "bench_cifar10", tag, args.batch, (3, 32, 32), 10
-        )
-        # reference OOD recipe: half the batch is corrupted, so the model
-        # has real faults for the APFD quality signal
-        half = args.batch // 2
-        px[half:] = corrupt_images("bench_cifar10", px[half:], severity=0.5)
+        px, py = pool_f[i].result()
+        pool_f[i] = None
         t = torch.from_numpy(px)
         if nhwc_pool:
             t = t.permute(0, 2, 3, 1).contiguous()
@@ -537,44 +644,15 @@ def main():
     total_inputs = per_step_inputs * args.steps
     value = total_inputs / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+    log(rank, f"timed x{args.steps}: {ms_per_step:.3f} ms/step")
 
-    # auxiliary quality signal: APFD of the gini ordering on the last batch
-    gini, _, _, pred = last
-    last_labels = labels_pool[(args.warmup + args.steps - 1) % len(pool)]
-    mis = (pred.cpu().numpy() != last_labels.numpy())
-    def _apfd(scores):
-        if not mis.any():
-            return float("nan")
-        return apfd_from_order(
-            mis, np.argsort(-scores.float().cpu().numpy(), kind="stable")
-        )
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
-    apfd = _apfd(gini)
-    _, dsa_last, lsa_last, _ = last
-    apfd_dsa = _apfd(dsa_last)
-    apfd_lsa = _apfd(lsa_last) if lsa_last is not None else float("nan")
-    # quality pin: on the NOMINAL half of the batch a
-    # trained model's deep-gini ordering must beat random — rules out a
-    # sign/negation bug producing a plausible-looking throughput number
-    half = args.batch // 2
-    mis_nom = mis[:half]
-    apfd_gini_nom = float("nan")
-    if mis_nom.sum() >= 10:
-        apfd_gini_nom = apfd_from_order(
-            mis_nom,
-            np.argsort(-gini[:half].float().cpu().numpy(), kind="stable"),
-        )
-        # assert only on statistically meaningful configs: a large nominal
-        # half and a model that actually learned (tiny smoke configs train
-        # for seconds and gini on a near-random model IS near-random)
-        if half >= 2000 and mis_nom.mean() < 0.5:
-            assert apfd_gini_nom > 0.5, (
-                f"deep-gini nominal APFD {apfd_gini_nom:.3f} <= 0.5: softmax "
-                f"ordering is not ranking real faults"
-            )
-    log(rank, f"last-batch accuracy={1.0 - mis.mean():.3f} "
-              f"apfd_gini={apfd:.3f} apfd_gini_nominal={apfd_gini_nom:.3f} "
-              f"apfd_dsa={apfd_dsa:.3f} apfd_lsa={apfd_lsa:.3f}")
+    quality = dict.fromkeys(QUALITY_KEYS)
+    if args.full:
+        last_labels = labels_pool[(args.warmup + args.steps - 1) % len(pool)]
+        quality = quality_signals(rank, last, last_labels, args.batch)
 
     if rank == 0:
         print(
@@ -606,12 +684,7 @@ def main():
                             else "hbm"
                         ),
                         "scorers": "gini+softmax-family+dsa+pc-lsa",
-                        "apfd_gini_lastbatch": None if np.isnan(apfd) else apfd,
-                        "apfd_gini_nominal_lastbatch": (
-                            None if np.isnan(apfd_gini_nom) else apfd_gini_nom
-                        ),
-                        "apfd_dsa_lastbatch": None if np.isnan(apfd_dsa) else apfd_dsa,
-                        "apfd_pclsa_lastbatch": None if np.isnan(apfd_lsa) else apfd_lsa,
+                        **quality,  # null unless --full
                     },
                 }
             ),
