@@ -32,6 +32,19 @@ MAX_NUM_MODELS = 100
 #: (reference: handler_model.py:7)
 DROPOUT_SAMPLE_SIZE = 200
 
+#: How BaseModel computes the MC-dropout variation ratio when it is not told:
+#: "replay" (re-run the whole model per sample), "fused" (trunk once + the
+#: mc_dropout_votes kernel; Dropout->Linear heads only) or "auto" (fused
+#: where applicable, else replay). Override with TIP_VR_MODE.
+VR_MODES = ("replay", "fused", "auto")
+
+
+def _default_vr_mode() -> str:
+    return os.environ.get("TIP_VR_MODE") or "replay"
+
+
+VR_MODE = _default_vr_mode()
+
 #: Number of surprise-coverage buckets (reference: handler_surprise.py:14)
 NUM_SC_BUCKETS = 1000
 

@@ -119,8 +119,11 @@ def _eval_fault_predictors(
         import torch
 
         n = ds.shape[0]
+        shard = shard_slice(n)
+        # row_base keeps the fused VR masks keyed by GLOBAL row, so a sharded
+        # run reproduces the single-rank scores
         pred_l, unc_l, times = base_model.get_pred_and_uncertainty(
-            ds[shard_slice(n)]
+            ds[shard], row_base=shard.start
         )
         pred = allgather_rows(torch.from_numpy(pred_l), n).numpy()
         uncertainties = {

@@ -7,7 +7,10 @@ MI355X-native differences:
 - the four point-prediction quantifiers are one fused epilogue over the
   softmax (ops.softmax_uncertainties — the K14 kernel on device);
 - MC-dropout variation ratio runs DROPOUT_SAMPLE_SIZE stochastic forwards
-  with device RNG and on-device vote counting.
+  with device RNG and on-device vote counting ("replay", the default), or,
+  for models that end in Dropout -> Linear, runs the deterministic trunk once
+  and all masked heads in one kernel (``vr_mode="fused"``,
+  ops.mc_dropout_votes: seeded, batch- and shard-invariant).
 Timing taxonomy is the reference's: per metric [setup, pred, quant, cam].
 """
 
@@ -18,6 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import config
 from ..config import DROPOUT_SAMPLE_SIZE
 from ..core.timer import DeviceTimer
 from .. import ops
@@ -43,7 +47,22 @@ class BaseModel:
         include_last_layer: bool = False,
         device: Optional[torch.device] = None,
         predict_batch: int = 512,
+        vr_mode: Optional[str] = None,
+        vr_seed: int = 0,
     ):
+        """``vr_mode`` selects how the variation ratio is sampled: "replay"
+        (whole model per sample), "fused" (trunk once + mc_dropout_votes;
+        ValueError unless the model ends in Dropout -> Linear within the
+        kernel envelope), "auto" (fused where applicable, else replay) or
+        None (``config.VR_MODE``). ``vr_seed`` seeds the fused masks."""
+        if vr_mode is None:
+            vr_mode = config.VR_MODE
+        if vr_mode not in config.VR_MODES:
+            raise ValueError(
+                f"vr_mode must be one of {config.VR_MODES}, got {vr_mode!r}"
+            )
+        self.vr_mode = vr_mode
+        self.vr_seed = int(vr_seed)
         self.model = model
         self.activation_layers = list(activation_layers) if activation_layers else None
         self.include_last_layer = include_last_layer
@@ -51,6 +70,8 @@ class BaseModel:
         self.predict_batch = predict_batch
         self._graphed = None  # lazy GraphedExtractor (GPU fast path, K15)
         self.model.eval()
+        if self.vr_mode == "fused":
+            self._fused_vr_head()  # fail at construction, not mid-run
 
     def _to_device(self, x) -> torch.Tensor:
         if not isinstance(x, torch.Tensor):
@@ -119,11 +140,13 @@ class BaseModel:
 
     @torch.no_grad()
     def get_pred_and_uncertainty(
-        self, x
+        self, x, row_base: int = 0
     ) -> Tuple[np.ndarray, Dict[str, np.ndarray], Dict[str, List[float]]]:
         """Point predictions + all uncertainty scores + per-metric times.
 
         Returns (pred, {metric: scores}, {metric: [setup, pred, quant, cam]}).
+        ``row_base`` is the global index of ``x[0]`` when ``x`` is a shard of
+        a larger dataset; only the fused VR path uses it (mask row ids).
         """
         pred_timer = DeviceTimer()
         quant_timer = DeviceTimer()
@@ -149,7 +172,7 @@ class BaseModel:
         }
 
         if self.model.has_dropout():
-            vr, vr_times = self._variation_ratio(x)
+            vr, vr_times = self._variation_ratio(x, row_base=row_base)
             uncertainties["VR"] = vr
             times["VR"] = vr_times
         else:
@@ -158,8 +181,92 @@ class BaseModel:
             )
         return pred, uncertainties, times
 
+    def _fused_vr_head(self) -> Optional[Tuple[int, float, nn.Linear]]:
+        """The Dropout -> Linear head to fuse, or None for the replay path.
+
+        Raises ValueError in "fused" mode when the model has no such head or
+        the head is outside the kernel envelope on this device."""
+        if self.vr_mode == "replay":
+            return None
+        head = self.model.dropout_head()
+        if head is None:
+            if self.vr_mode == "fused":
+                raise ValueError(
+                    'vr_mode="fused" needs a model whose only Dropout feeds '
+                    "the final Linear layer (TapModel.dropout_head() is None "
+                    f"for {type(self.model).__name__})"
+                )
+            return None
+        lin = head[2]
+        if not ops.mc_dropout_supported(
+            lin.weight, lin.out_features, lin.in_features
+        ):
+            if self.vr_mode == "fused":
+                raise ValueError(
+                    'vr_mode="fused": the head Linear'
+                    f"({lin.in_features}, {lin.out_features}) is outside the "
+                    "mc_dropout_votes kernel envelope (C <= 16, D <= 2048)"
+                )
+            return None
+        return head
+
     @torch.no_grad()
-    def _variation_ratio(self, x) -> Tuple[np.ndarray, List[float]]:
+    def _variation_ratio(
+        self, x, row_base: int = 0
+    ) -> Tuple[np.ndarray, List[float]]:
+        """MC-dropout variation ratio over DROPOUT_SAMPLE_SIZE samples."""
+        head = self._fused_vr_head()
+        if head is not None:
+            return self._variation_ratio_fused(x, head, row_base)
+        return self._variation_ratio_replay(x)
+
+    @torch.no_grad()
+    def _variation_ratio_fused(
+        self, x, head, row_base: int
+    ) -> Tuple[np.ndarray, List[float]]:
+        """Trunk once per batch, then all masked heads in one kernel."""
+        k, p, lin = head
+        sampling_timer = DeviceTimer()
+        quant_timer = DeviceTimer()
+        self.model.eval()
+        use_amp = self.device.type == "cuda"
+        bias = lin.bias
+        if bias is None:
+            bias = torch.zeros(lin.out_features, device=lin.weight.device)
+        parts: List[torch.Tensor] = []
+        with sampling_timer:
+            for s0 in range(0, x.shape[0], self.predict_batch):
+                h = self._to_device(x[s0 : s0 + self.predict_batch])
+                with torch.autocast("cuda", dtype=torch.bfloat16,
+                                    enabled=use_amp):
+                    for layer in self.model.layers[:k]:
+                        h = layer(h)
+                parts.append(
+                    ops.mc_dropout_votes(
+                        h.float().reshape(h.shape[0], -1),
+                        lin.weight.float(),
+                        bias.float(),
+                        p,
+                        DROPOUT_SAMPLE_SIZE,
+                        self.vr_seed,
+                        row_offset=int(row_base) + s0,
+                    )
+                )
+        with quant_timer:
+            if not parts:
+                parts.append(torch.zeros(
+                    0, lin.out_features, dtype=torch.int32, device=self.device
+                ))
+            counts = torch.cat(parts, dim=0)
+            top = counts.max(dim=1).values.float()
+            vr = 1.0 - top / float(DROPOUT_SAMPLE_SIZE)
+        return (
+            vr.cpu().numpy(),
+            [0.0, sampling_timer.get(), quant_timer.get(), 0.0],
+        )
+
+    @torch.no_grad()
+    def _variation_ratio_replay(self, x) -> Tuple[np.ndarray, List[float]]:
         """MC-dropout variation ratio over DROPOUT_SAMPLE_SIZE forwards."""
         sampling_timer = DeviceTimer()
         quant_timer = DeviceTimer()

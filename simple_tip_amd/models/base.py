@@ -55,3 +55,22 @@ class TapModel(nn.Module):
     def has_dropout(self) -> bool:
         """Whether MC-dropout sampling (variation ratio) is applicable."""
         return any(isinstance(m, nn.Dropout) for m in self.modules())
+
+    def dropout_head(self) -> Optional[Tuple[int, float, nn.Linear]]:
+        """``(k, p, linear)`` if the model ends in Dropout -> Linear.
+
+        Applies when ``layers[k]`` is an ``nn.Dropout``, ``layers[k+1]`` is
+        the final layer and an ``nn.Linear``, and the model holds no other
+        ``nn.Dropout`` anywhere. Then all MC-dropout samples of an input
+        share the output of ``layers[:k]`` and differ only in the masked
+        linear head (``ops.mc_dropout_votes``). Otherwise ``None``.
+        """
+        k = len(self.layers) - 2
+        if k < 0:
+            return None
+        drop, last = self.layers[k], self.layers[k + 1]
+        if not isinstance(drop, nn.Dropout) or not isinstance(last, nn.Linear):
+            return None
+        if sum(isinstance(m, nn.Dropout) for m in self.modules()) != 1:
+            return None
+        return k, float(drop.p), last

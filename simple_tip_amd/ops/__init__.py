@@ -114,6 +114,39 @@ def variation_ratio(sample_preds: torch.Tensor, num_classes: int):
     return fallback.variation_ratio(sample_preds, num_classes)
 
 
+def mc_dropout_votes(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> torch.Tensor:
+    """Votes [N, C] (int32) of ``num_samples`` dropout-masked linear heads.
+
+    Masks come from a stateless hash of (seed, sample, row_offset + n, d), so
+    the result is reproducible and independent of batching and sharding. On
+    GPU tensors the head must fit the kernel envelope (C <= 16, D <= 2048):
+    outside it the call raises ValueError, it never falls back.
+    """
+    return _route(feats).mc_dropout_votes(
+        feats, weight, bias, p, num_samples, seed, row_offset
+    )
+
+
+def mc_dropout_supported(t: torch.Tensor, C: int, D: int) -> bool:
+    """Whether a [C, D] head on ``t``'s device is inside the op's envelope."""
+    impl = _route(t)
+    if impl is fallback:
+        return True
+    try:
+        impl.mc_dropout_check_envelope(C, D)
+    except ValueError:
+        return False
+    return True
+
+
 def nac_profile(acts: torch.Tensor, threshold: float) -> torch.Tensor:
     return _route(acts).nac_profile(acts.contiguous(), threshold)
 

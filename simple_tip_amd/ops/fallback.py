@@ -223,6 +223,123 @@ def variation_ratio(sample_preds: torch.Tensor, num_classes: int) -> Tuple[torch
 
 
 # ---------------------------------------------------------------------------
+# Fused MC-dropout head (variation-ratio votes)
+# ---------------------------------------------------------------------------
+
+_M32 = 0xFFFFFFFF
+# cap on mask elements materialised at once by mc_dropout_votes (the hash
+# runs on int64 temporaries, so 16M elements is ~128 MiB per temporary)
+_MCD_MAX_MASK_ELEMS = 16 * 1024 * 1024
+
+
+def _mix32(x: torch.Tensor) -> torch.Tensor:
+    """32-bit finalizer on int64 tensors holding values in [0, 2^32)."""
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & _M32
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & _M32
+    x = x ^ (x >> 16)
+    return x
+
+
+def dropout_threshold(p: float) -> int:
+    """T = floor(p * 2^32) in float64; an element is kept iff word >= T."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    return int(float(p) * 4294967296.0)
+
+
+def dropout_scale(p: float) -> float:
+    """1 / (1 - p) rounded to float32 (returned as an exact python float)."""
+    return float(np.float32(1.0 / (1.0 - float(p))))
+
+
+def dropout_words(
+    seed: int, S: int, N: int, D: int, row_offset: int = 0
+) -> torch.Tensor:
+    """The stateless generator's 32-bit words, int64 [S, N, D].
+
+    All arithmetic is unsigned 32-bit (wrapping), carried in int64 tensors
+    masked to 32 bits::
+
+        r    = mix32(mix32(mix32(g + 0x6A09E667) ^ lo) ^ hi)    g = row_offset + n
+        key  = mix32(r + s * 0x9E3779B9)
+        word = mix32(key ^ (d * 0x85EBCA6B))
+    """
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lo, hi = seed & _M32, seed >> 32
+    g = (torch.arange(N, dtype=torch.int64) + int(row_offset)) & _M32
+    r = _mix32((g + 0x6A09E667) & _M32)
+    r = _mix32(r ^ lo)
+    r = _mix32(r ^ hi)
+    s = torch.arange(S, dtype=torch.int64)
+    key = _mix32((r[None, :] + ((s * 0x9E3779B9) & _M32)[:, None]) & _M32)
+    d = (torch.arange(D, dtype=torch.int64) * 0x85EBCA6B) & _M32
+    return _mix32(key[:, :, None] ^ d[None, None, :])
+
+
+def dropout_keep_mask(
+    seed: int, S: int, N: int, D: int, p: float, row_offset: int = 0
+) -> torch.Tensor:
+    """Keep mask of the MC-dropout head, bool [S, N, D] (True = kept).
+
+    Depends only on (seed, sample, global row, feature) — never on batch
+    size or sharding. The HIP kernel generates the same bits in registers.
+    """
+    return dropout_words(seed, S, N, D, row_offset) >= dropout_threshold(p)
+
+
+def mc_dropout_votes(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> torch.Tensor:
+    """Argmax votes of ``num_samples`` dropout-masked linear heads, int32 [N, C].
+
+    ``logit[c] = scale * sum_d keep*feats[n,d]*weight[c,d] + bias[c]`` with
+    ``scale = 1/(1-p)`` (float32) applied once after the sum; the vote goes
+    to the lowest index among the maximal logits. Inputs must be finite
+    (votes of a row with NaN/inf logits are unspecified). Rows are processed
+    in chunks so only ``_MCD_MAX_MASK_ELEMS`` mask elements exist at a time.
+    """
+    n, d = feats.shape
+    c = weight.shape[0]
+    S = int(num_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"num_samples must be in [1, 65535], got {S}")
+    if row_offset < 0 or row_offset + n > 2 ** 32:
+        raise ValueError("rows must satisfy row_offset + N <= 2^32")
+    thresh = dropout_threshold(p)
+    scale = dropout_scale(p)
+    dev = feats.device
+    f = feats.detach().float().cpu()
+    wt = weight.detach().float().cpu().t().contiguous()
+    b = bias.detach().float().cpu()
+    votes = torch.zeros(n, c, dtype=torch.int32)
+    rows = max(1, _MCD_MAX_MASK_ELEMS // max(1, S * d))
+    ones = torch.ones(1, dtype=torch.int32)
+    cls = torch.arange(c, dtype=torch.int64)
+    for s0 in range(0, n, rows):
+        fb = f[s0 : s0 + rows]
+        nb = fb.shape[0]
+        keep = dropout_words(seed, S, nb, d, row_offset + s0) >= thresh
+        sums = torch.matmul(keep.to(torch.float32) * fb[None], wt)  # [S,nb,C]
+        logits = scale * sums + b
+        # first maximal index (torch.argmax does not promise one on ties)
+        is_max = logits == logits.max(dim=2, keepdim=True).values
+        best = torch.where(is_max, cls, c).min(dim=2).values  # [S, nb]
+        best.clamp_(max=c - 1)  # NaN logits match nothing; keep the index valid
+        votes[s0 : s0 + nb].scatter_add_(
+            1, best.t().contiguous(), ones.expand(nb, S)
+        )
+    return votes.to(dev)
+
+
+# ---------------------------------------------------------------------------
 # Coverage profiling (bool → packed bitmaps)
 # ---------------------------------------------------------------------------
 

@@ -61,6 +61,13 @@ void launch_downblock(int, int, const short*, short*, const short*,
                       const float*, hipStream_t);
 void launch_stem(int, const short*, short*, const short*, const float*,
                  hipStream_t);
+void launch_mc_dropout_votes(const float*, const float*, const float*, int,
+                             int, int, int, uint32_t, float, uint32_t,
+                             uint32_t, uint32_t, int*, hipStream_t);
+int mc_dropout_max_grid(int, int);
+int mc_dropout_rows_per_block();
+int mc_dropout_max_classes();
+int mc_dropout_max_features();
 
 namespace {
 
@@ -488,6 +495,42 @@ torch::Tensor resnet_stem(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
   return out;
 }
 
+// ---- fused MC-dropout head (variation-ratio votes) ----
+
+// thresh = floor(p * 2^32) and scale = float32(1 / (1 - p)) are computed once
+// by the Python wrapper so the CPU oracle and the kernel share the exact bits.
+torch::Tensor mc_dropout_votes(torch::Tensor feats, torch::Tensor weight,
+                               torch::Tensor bias, int64_t thresh,
+                               double scale, int64_t num_samples,
+                               int64_t seed_lo, int64_t seed_hi,
+                               int64_t row_offset) {
+  check_f32_2d(feats, "feats");
+  check_f32_2d(weight, "weight");
+  TORCH_CHECK(bias.is_cuda() && bias.dtype() == torch::kFloat32 &&
+                  bias.dim() == 1 && bias.is_contiguous(),
+              "bias must be a contiguous 1D fp32 GPU tensor");
+  const int64_t n = feats.size(0), d = feats.size(1), c = weight.size(0);
+  TORCH_CHECK(weight.size(1) == d, "weight must be [C, D]");
+  TORCH_CHECK(bias.size(0) == c, "bias must be [C]");
+  TORCH_CHECK(c >= 1 && c <= mc_dropout_max_classes() && d >= 1 &&
+                  d <= mc_dropout_max_features(),
+              "mc_dropout_votes envelope is C <= ", mc_dropout_max_classes(),
+              ", D <= ", mc_dropout_max_features());
+  TORCH_CHECK(num_samples >= 1 && num_samples <= 65535, "bad num_samples");
+  TORCH_CHECK(thresh >= 0 && thresh <= 0xFFFFFFFFll, "bad threshold");
+  TORCH_CHECK(n <= 0x7FFFFFFFll && row_offset >= 0 &&
+                  row_offset + n <= 0x100000000ll,
+              "rows must satisfy row_offset + N <= 2^32");
+  auto votes = torch::empty({n, c}, feats.options().dtype(torch::kInt32));
+  if (n == 0) return votes;
+  launch_mc_dropout_votes(
+      feats.data_ptr<float>(), weight.data_ptr<float>(),
+      bias.data_ptr<float>(), (int)n, (int)d, (int)c, (int)num_samples,
+      (uint32_t)thresh, (float)scale, (uint32_t)seed_lo, (uint32_t)seed_hi,
+      (uint32_t)row_offset, votes.data_ptr<int>(), cur_stream());
+  return votes;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -513,4 +556,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resnet_block", &resnet_block);
   m.def("resnet_down", &resnet_down);
   m.def("resnet_stem", &resnet_stem);
+  m.def("mc_dropout_votes", &mc_dropout_votes);
+  m.def("mc_dropout_max_grid", &mc_dropout_max_grid);
+  m.def("mc_dropout_rows_per_block", &mc_dropout_rows_per_block);
+  m.def("mc_dropout_max_classes", &mc_dropout_max_classes);
+  m.def("mc_dropout_max_features", &mc_dropout_max_features);
 }

@@ -80,6 +80,78 @@ def variation_ratio(sample_preds: torch.Tensor, num_classes: int):
     return fallback.variation_ratio(sample_preds, num_classes)
 
 
+#: device envelope of the fused MC-dropout head (mcdropout.hip): the
+#: transposed weights [D][C padded to 4] plus the bias row must fit in LDS
+MC_DROPOUT_MAX_CLASSES = _ext.mc_dropout_max_classes()
+MC_DROPOUT_MAX_FEATURES = _ext.mc_dropout_max_features()
+
+
+def mc_dropout_launch_config(D: int, C: int) -> Dict[str, int]:
+    """Launch constants of ``mc_dropout_votes`` on the current device.
+
+    One wave handles one row; a block holds ``rows_per_block`` waves and the
+    grid is capped at ``max_grid`` blocks, so ``rows_per_pass`` rows are in
+    flight and the grid-stride row loop runs ``ceil(N / rows_per_pass)``
+    passes.
+    """
+    rows_per_block = _ext.mc_dropout_rows_per_block()
+    max_grid = _ext.mc_dropout_max_grid(int(D), int(C))
+    return {
+        "rows_per_block": rows_per_block,
+        "max_grid": max_grid,
+        "rows_per_pass": rows_per_block * max_grid,
+    }
+
+
+def mc_dropout_check_envelope(C: int, D: int) -> None:
+    """Raise ValueError if a [C, D] head is outside the kernel's envelope."""
+    if not (1 <= C <= MC_DROPOUT_MAX_CLASSES and 1 <= D <= MC_DROPOUT_MAX_FEATURES):
+        raise ValueError(
+            f"mc_dropout_votes on GPU supports C <= {MC_DROPOUT_MAX_CLASSES} "
+            f"classes and D <= {MC_DROPOUT_MAX_FEATURES} features "
+            f"(got C={C}, D={D})"
+        )
+
+
+def mc_dropout_votes(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> torch.Tensor:
+    from . import fallback
+
+    if feats.dim() != 2 or weight.dim() != 2 or bias.dim() != 1:
+        raise ValueError("expected feats [N, D], weight [C, D], bias [C]")
+    n, d = feats.shape
+    c = weight.shape[0]
+    if weight.shape[1] != d or bias.shape[0] != c:
+        raise ValueError("weight must be [C, D] and bias [C]")
+    mc_dropout_check_envelope(c, d)
+    S = int(num_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"num_samples must be in [1, 65535], got {S}")
+    row_offset = int(row_offset)
+    if row_offset < 0 or row_offset + n > 2 ** 32:
+        raise ValueError("rows must satisfy row_offset + N <= 2^32")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    dev = feats.device
+    return _ext.mc_dropout_votes(
+        feats.float().contiguous(),
+        weight.to(dev).float().contiguous(),
+        bias.to(dev).float().contiguous(),
+        fallback.dropout_threshold(p),
+        fallback.dropout_scale(p),
+        S,
+        seed & 0xFFFFFFFF,
+        seed >> 32,
+        row_offset,
+    )
+
+
 def _empty(t):
     return torch.empty(0, dtype=torch.float32, device=t.device)
 
