@@ -6,7 +6,9 @@ Times, on one GPU and in one process:
     modes alternating over ``--reps`` repetitions after one warm-up each;
   - the ``mc_dropout_votes`` kernel alone on [N, 1600] x [10, 1600], on the
     model's own trunk features and on two synthetic feature sets that bound
-    the zero-skip (relu(randn): half zero; |randn|: no zeros).
+    the zero-skip (relu(randn): half zero; |randn|: no zeros);
+  - the ``mc_dropout_stats`` kernel (votes + mean softmax + mean entropy) on
+    the same three feature sets, each right after its votes timing.
 
 Every window ends in a device synchronise. Prints one JSON line.
 
@@ -39,9 +41,9 @@ def wall_ms(fn):
     return (time.perf_counter() - t0) * 1000.0, out
 
 
-def kernel_ms(feats, weight, bias, iters):
-    """Median device-event time of one mc_dropout_votes call."""
-    call = lambda: ops.mc_dropout_votes(  # noqa: E731
+def kernel_ms(feats, weight, bias, iters, op=ops.mc_dropout_votes):
+    """Median device-event time of one mc_dropout_votes / _stats call."""
+    call = lambda: op(  # noqa: E731
         feats, weight, bias, 0.5, DROPOUT_SAMPLE_SIZE, 0
     )
     call()
@@ -118,6 +120,7 @@ def main():
         "abs_randn": randn.abs(),
     }
     kernel = {}
+    kernel_stats = {}
     for name, feats in feature_sets.items():
         med, lo, hi = kernel_ms(feats, weight, bias, args.kernel_iters)
         kernel[name] = {
@@ -125,6 +128,15 @@ def main():
             "median_ms": round(med, 3),
             "min_ms": round(lo, 3),
             "max_ms": round(hi, 3),
+        }
+        med_s, lo_s, hi_s = kernel_ms(
+            feats, weight, bias, args.kernel_iters, op=ops.mc_dropout_stats
+        )
+        kernel_stats[name] = {
+            "median_ms": round(med_s, 3),
+            "min_ms": round(lo_s, 3),
+            "max_ms": round(hi_s, 3),
+            "over_votes": round(med_s / med, 3),
         }
 
     med_r = statistics.median(t_replay)
@@ -141,6 +153,7 @@ def main():
         "speedup_median": round(med_r / med_f, 2),
         "speedup_worst_case": round(min(t_replay) / max(t_fused), 2),
         "kernel": kernel,
+        "kernel_stats": kernel_stats,
         "mean_vr_replay": round(float(vr_r.mean()), 4),
         "mean_vr_fused": round(float(vr_f.mean()), 4),
         "launch": hip_ops.mc_dropout_launch_config(

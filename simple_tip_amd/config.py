@@ -45,6 +45,22 @@ def _default_vr_mode() -> str:
 
 VR_MODE = _default_vr_mode()
 
+#: Sampling quantifiers BaseModel derives from the MC-dropout samples when it
+#: is not told: "VR" (variation ratio; always computed), "PE" (predictive
+#: entropy), "MI" (mutual information) and "MS" (negated max of the mean
+#: softmax). Override with TIP_MC_QUANTIFIERS, a comma list ("VR,PE,MI").
+MC_QUANTIFIER_NAMES = ("VR", "PE", "MI", "MS")
+
+
+def _default_mc_quantifiers() -> tuple:
+    env = os.environ.get("TIP_MC_QUANTIFIERS")
+    if not env:
+        return ("VR",)
+    return tuple(name.strip() for name in env.split(",") if name.strip())
+
+
+MC_QUANTIFIERS = _default_mc_quantifiers()
+
 #: Number of surprise-coverage buckets (reference: handler_surprise.py:14)
 NUM_SC_BUCKETS = 1000
 

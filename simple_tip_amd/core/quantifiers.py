@@ -86,6 +86,82 @@ class VariationRatio(Quantifier):
         return mode, vr
 
 
+def probs_entropy(probs: torch.Tensor) -> torch.Tensor:
+    """-sum p log p over the last dim (natural log, 0 log 0 = 0)."""
+    logp = torch.where(probs > 0, torch.log(probs), torch.zeros_like(probs))
+    return -(probs * logp).sum(dim=-1)
+
+
+def _first_argmax(t: torch.Tensor) -> torch.Tensor:
+    """Row argmax of [N, C], lowest index on ties."""
+    c = t.shape[1]
+    idx = torch.arange(c, device=t.device)
+    is_max = t == t.max(dim=1, keepdim=True).values
+    return torch.where(is_max, idx, c).min(dim=1).values.clamp_(max=c - 1)
+
+
+def mc_sample_scores(
+    mean_probs: torch.Tensor, mean_entropy: torch.Tensor
+) -> Dict[str, torch.Tensor]:
+    """The sampling quantifications from the two sample statistics.
+
+    ``mean_probs`` [N, C] is the mean over the samples of the softmax
+    outputs, ``mean_entropy`` [N] the mean of the samples' entropies (what
+    ``ops.mc_dropout_stats`` returns, or what a replay loop accumulates).
+    Returns ``pred`` (argmax of the mean, lowest index on ties) and, with
+    higher = more uncertain, ``PE`` = H(mean), ``MI`` = H(mean) - mean
+    entropy and ``MS`` = -max(mean).
+    """
+    pe = probs_entropy(mean_probs)
+    return {
+        "pred": _first_argmax(mean_probs),
+        "PE": pe,
+        "MI": pe - mean_entropy,
+        "MS": -mean_probs.max(dim=1).values,
+    }
+
+
+def _sample_stats(sample_probs: torch.Tensor):
+    """[S, N, C] probabilities -> (mean over samples, mean sample entropy)."""
+    return sample_probs.mean(dim=0), probs_entropy(sample_probs).mean(dim=0)
+
+
+class MeanSoftmax(Quantifier):
+    """Max of the mean softmax over MC samples [S, N, C] (a confidence)."""
+
+    aliases = ["mean_softmax", "MeanSoftmax", "ensembling"]
+    is_confidence = True
+    takes_samples = True
+
+    def calculate(self, sample_probs):
+        s = mc_sample_scores(*_sample_stats(sample_probs))
+        return s["pred"], -s["MS"]
+
+
+class PredictiveEntropy(Quantifier):
+    """Entropy of the mean softmax over MC samples [S, N, C]."""
+
+    aliases = ["predictive_entropy", "pred_entropy", "PE", "PredictiveEntropy"]
+    is_confidence = False
+    takes_samples = True
+
+    def calculate(self, sample_probs):
+        s = mc_sample_scores(*_sample_stats(sample_probs))
+        return s["pred"], s["PE"]
+
+
+class MutualInformation(Quantifier):
+    """BALD: entropy of the mean minus the mean entropy of the samples."""
+
+    aliases = ["mutual_information", "mutu_info", "MI", "MutualInformation"]
+    is_confidence = False
+    takes_samples = True
+
+    def calculate(self, sample_probs):
+        s = mc_sample_scores(*_sample_stats(sample_probs))
+        return s["pred"], s["MI"]
+
+
 class QuantifierRegistry:
     """Alias -> quantifier lookup; extensible like the uwiz registry."""
 
@@ -104,5 +180,6 @@ class QuantifierRegistry:
 
 
 for _q in (MaxSoftmax(), PredictionConfidenceScore(), SoftmaxEntropy(),
-           DeepGini(), VariationRatio()):
+           DeepGini(), VariationRatio(), MeanSoftmax(), PredictiveEntropy(),
+           MutualInformation()):
     QuantifierRegistry.register(_q)

@@ -10,7 +10,11 @@ MI355X-native differences:
   with device RNG and on-device vote counting ("replay", the default), or,
   for models that end in Dropout -> Linear, runs the deterministic trunk once
   and all masked heads in one kernel (``vr_mode="fused"``,
-  ops.mc_dropout_votes: seeded, batch- and shard-invariant).
+  ops.mc_dropout_votes: seeded, batch- and shard-invariant);
+- the other sampling quantifiers (predictive entropy, mutual information,
+  mean softmax) are opt-in (``mc_quantifiers``) and come from the same
+  samples: on the fused path one ops.mc_dropout_stats call per batch
+  replaces the votes call, on replay the loop also sums the softmax outputs.
 Timing taxonomy is the reference's: per metric [setup, pred, quant, cam].
 """
 
@@ -23,6 +27,7 @@ import torch.nn as nn
 
 from .. import config
 from ..config import DROPOUT_SAMPLE_SIZE
+from ..core.quantifiers import probs_entropy, mc_sample_scores
 from ..core.timer import DeviceTimer
 from .. import ops
 from ..models.base import TapModel
@@ -49,12 +54,32 @@ class BaseModel:
         predict_batch: int = 512,
         vr_mode: Optional[str] = None,
         vr_seed: int = 0,
+        mc_quantifiers: Optional[Sequence[str]] = None,
     ):
         """``vr_mode`` selects how the variation ratio is sampled: "replay"
         (whole model per sample), "fused" (trunk once + mc_dropout_votes;
         ValueError unless the model ends in Dropout -> Linear within the
         kernel envelope), "auto" (fused where applicable, else replay) or
-        None (``config.VR_MODE``). ``vr_seed`` seeds the fused masks."""
+        None (``config.VR_MODE``). ``vr_seed`` seeds the fused masks.
+        ``mc_quantifiers`` names the sampling scores to return, out of "VR",
+        "PE" (predictive entropy), "MI" (mutual information) and "MS"
+        (negated max of the mean softmax); None means
+        ``config.MC_QUANTIFIERS``. "VR" is always computed."""
+        if mc_quantifiers is None:
+            mc_quantifiers = config.MC_QUANTIFIERS
+        mc_quantifiers = tuple(mc_quantifiers)
+        unknown = [q for q in mc_quantifiers if q not in config.MC_QUANTIFIER_NAMES]
+        if unknown:
+            raise ValueError(
+                f"mc_quantifiers must be among {config.MC_QUANTIFIER_NAMES}, "
+                f"got {unknown!r}"
+            )
+        self.mc_quantifiers = mc_quantifiers
+        # the scores beyond VR, in canonical order
+        self._mc_extras = tuple(
+            q for q in config.MC_QUANTIFIER_NAMES
+            if q != "VR" and q in mc_quantifiers
+        )
         if vr_mode is None:
             vr_mode = config.VR_MODE
         if vr_mode not in config.VR_MODES:
@@ -146,7 +171,9 @@ class BaseModel:
 
         Returns (pred, {metric: scores}, {metric: [setup, pred, quant, cam]}).
         ``row_base`` is the global index of ``x[0]`` when ``x`` is a shard of
-        a larger dataset; only the fused VR path uses it (mask row ids).
+        a larger dataset; only the fused sampling path uses it (mask row
+        ids). The sampling scores requested with ``mc_quantifiers`` beyond
+        "VR" appear under "PE", "MI" and "MS" (higher = more uncertain).
         """
         pred_timer = DeviceTimer()
         quant_timer = DeviceTimer()
@@ -172,9 +199,15 @@ class BaseModel:
         }
 
         if self.model.has_dropout():
-            vr, vr_times = self._variation_ratio(x, row_base=row_base)
-            uncertainties["VR"] = vr
-            times["VR"] = vr_times
+            if self._mc_extras:
+                mc, mc_times = self._mc_scores(x, row_base=row_base)
+                for k in ("VR",) + self._mc_extras:
+                    uncertainties[k] = mc[k]
+                    times[k] = list(mc_times)
+            else:
+                vr, vr_times = self._variation_ratio(x, row_base=row_base)
+                uncertainties["VR"] = vr
+                times["VR"] = vr_times
         else:
             logger.warning(
                 "No stochastic (dropout) layers in model; skipping VR."
@@ -221,10 +254,35 @@ class BaseModel:
         return self._variation_ratio_replay(x)
 
     @torch.no_grad()
+    def _mc_scores(
+        self, x, row_base: int = 0
+    ) -> Tuple[Dict[str, np.ndarray], List[float]]:
+        """VR plus the requested extra sampling scores, from one sampling
+        pass: ({"VR": ..., "PE": ..., ...}, [0, sampling, quant, 0])."""
+        head = self._fused_vr_head()
+        if head is not None:
+            return self._sample_fused(x, head, row_base, extras=True)
+        return self._sample_replay(x, extras=True)
+
+    def _extra_scores(self, mean_probs, mean_entropy) -> Dict[str, np.ndarray]:
+        """The requested extras as float32 numpy arrays."""
+        s = mc_sample_scores(mean_probs, mean_entropy)
+        return {k: s[k].float().cpu().numpy() for k in self._mc_extras}
+
+    @torch.no_grad()
     def _variation_ratio_fused(
         self, x, head, row_base: int
     ) -> Tuple[np.ndarray, List[float]]:
         """Trunk once per batch, then all masked heads in one kernel."""
+        scores, times = self._sample_fused(x, head, row_base, extras=False)
+        return scores["VR"], times
+
+    @torch.no_grad()
+    def _sample_fused(
+        self, x, head, row_base: int, extras: bool
+    ) -> Tuple[Dict[str, np.ndarray], List[float]]:
+        """Fused sampling: ops.mc_dropout_votes per batch, or, with
+        ``extras``, ops.mc_dropout_stats (its votes are the same votes)."""
         k, p, lin = head
         sampling_timer = DeviceTimer()
         quant_timer = DeviceTimer()
@@ -233,7 +291,10 @@ class BaseModel:
         bias = lin.bias
         if bias is None:
             bias = torch.zeros(lin.out_features, device=lin.weight.device)
+        head_op = ops.mc_dropout_stats if extras else ops.mc_dropout_votes
         parts: List[torch.Tensor] = []
+        prob_parts: List[torch.Tensor] = []
+        ent_parts: List[torch.Tensor] = []
         with sampling_timer:
             for s0 in range(0, x.shape[0], self.predict_batch):
                 h = self._to_device(x[s0 : s0 + self.predict_batch])
@@ -241,33 +302,56 @@ class BaseModel:
                                     enabled=use_amp):
                     for layer in self.model.layers[:k]:
                         h = layer(h)
-                parts.append(
-                    ops.mc_dropout_votes(
-                        h.float().reshape(h.shape[0], -1),
-                        lin.weight.float(),
-                        bias.float(),
-                        p,
-                        DROPOUT_SAMPLE_SIZE,
-                        self.vr_seed,
-                        row_offset=int(row_base) + s0,
-                    )
+                out = head_op(
+                    h.float().reshape(h.shape[0], -1),
+                    lin.weight.float(),
+                    bias.float(),
+                    p,
+                    DROPOUT_SAMPLE_SIZE,
+                    self.vr_seed,
+                    row_offset=int(row_base) + s0,
                 )
+                if extras:
+                    parts.append(out[0])
+                    prob_parts.append(out[1])
+                    ent_parts.append(out[2])
+                else:
+                    parts.append(out)
         with quant_timer:
             if not parts:
                 parts.append(torch.zeros(
                     0, lin.out_features, dtype=torch.int32, device=self.device
                 ))
+                prob_parts.append(torch.zeros(
+                    0, lin.out_features, device=self.device
+                ))
+                ent_parts.append(torch.zeros(0, device=self.device))
             counts = torch.cat(parts, dim=0)
             top = counts.max(dim=1).values.float()
             vr = 1.0 - top / float(DROPOUT_SAMPLE_SIZE)
+            scores = {"VR": vr.cpu().numpy()}
+            if extras:
+                scores.update(self._extra_scores(
+                    torch.cat(prob_parts, dim=0), torch.cat(ent_parts, dim=0)
+                ))
         return (
-            vr.cpu().numpy(),
+            scores,
             [0.0, sampling_timer.get(), quant_timer.get(), 0.0],
         )
 
     @torch.no_grad()
     def _variation_ratio_replay(self, x) -> Tuple[np.ndarray, List[float]]:
         """MC-dropout variation ratio over DROPOUT_SAMPLE_SIZE forwards."""
+        scores, times = self._sample_replay(x, extras=False)
+        return scores["VR"], times
+
+    @torch.no_grad()
+    def _sample_replay(
+        self, x, extras: bool
+    ) -> Tuple[Dict[str, np.ndarray], List[float]]:
+        """DROPOUT_SAMPLE_SIZE stochastic forwards with on-device vote
+        counting; with ``extras`` the loop also sums the samples' softmax
+        outputs and entropies (float32 [b, C] / [b] sums per batch)."""
         sampling_timer = DeviceTimer()
         quant_timer = DeviceTimer()
         self.model.eval()
@@ -281,6 +365,13 @@ class BaseModel:
             counts = torch.zeros(
                 n, num_classes, dtype=torch.float32, device=self.device
             )
+            if extras:
+                prob_sums = torch.zeros(
+                    n, num_classes, dtype=torch.float32, device=self.device
+                )
+                ent_sums = torch.zeros(
+                    n, dtype=torch.float32, device=self.device
+                )
             with sampling_timer:
                 for s0 in range(0, n, self.predict_batch):
                     xb = self._to_device(x[s0 : s0 + self.predict_batch])
@@ -288,6 +379,11 @@ class BaseModel:
                     votes = torch.zeros(
                         b, num_classes, dtype=torch.float32, device=self.device
                     )
+                    if extras:
+                        psum = torch.zeros_like(votes)
+                        hsum = torch.zeros(
+                            b, dtype=torch.float32, device=self.device
+                        )
                     # vectorize the MC samples: R independent dropout
                     # replicas per forward pass (throughput, not 200 passes)
                     # macro-batch cap 8192: measured optimum (32768 made
@@ -309,13 +405,28 @@ class BaseModel:
                             preds.t(),
                             torch.ones(b, r, device=self.device),
                         )
+                        if extras:
+                            probs = torch.softmax(
+                                logits.float(), dim=1
+                            ).reshape(r, b, num_classes)
+                            psum += probs.sum(dim=0)
+                            hsum += probs_entropy(probs).sum(dim=0)
                         done += r
                     counts[s0 : s0 + b] = votes
+                    if extras:
+                        prob_sums[s0 : s0 + b] = psum
+                        ent_sums[s0 : s0 + b] = hsum
             with quant_timer:
                 top = counts.max(dim=1).values
                 vr = 1.0 - top / float(DROPOUT_SAMPLE_SIZE)
+                scores = {"VR": vr.cpu().numpy()}
+                if extras:
+                    scores.update(self._extra_scores(
+                        prob_sums / float(DROPOUT_SAMPLE_SIZE),
+                        ent_sums / float(DROPOUT_SAMPLE_SIZE),
+                    ))
             return (
-                vr.cpu().numpy(),
+                scores,
                 [0.0, sampling_timer.get(), quant_timer.get(), 0.0],
             )
         finally:

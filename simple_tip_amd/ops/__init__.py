@@ -135,6 +135,33 @@ def mc_dropout_votes(
     )
 
 
+def mc_dropout_stats(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Votes plus the sample statistics of the same dropout-masked heads.
+
+    Returns ``(votes int32 [N, C], mean_probs float32 [N, C], mean_entropy
+    float32 [N])``: ``votes`` is bit-identical to :func:`mc_dropout_votes`,
+    ``mean_probs`` is the mean over the samples of softmax(logits) and
+    ``mean_entropy`` the mean of the samples' softmax entropies (natural
+    log). Predictive entropy, mutual information and the mean-softmax
+    confidence follow from the last two
+    (``core.quantifiers.mc_sample_scores``). Same masks, envelope and
+    ``row_offset`` semantics as :func:`mc_dropout_votes`; on GPU tensors the
+    floats are reduced in a fixed order, so a row's result does not depend
+    on the batch it arrives in.
+    """
+    return _route(feats).mc_dropout_stats(
+        feats, weight, bias, p, num_samples, seed, row_offset
+    )
+
+
 def mc_dropout_supported(t: torch.Tensor, C: int, D: int) -> bool:
     """Whether a [C, D] head on ``t``'s device is inside the op's envelope."""
     impl = _route(t)

@@ -289,6 +289,59 @@ def dropout_keep_mask(
     return dropout_words(seed, S, N, D, row_offset) >= dropout_threshold(p)
 
 
+def _mc_dropout_eval(feats, weight, bias, p, num_samples, seed, row_offset,
+                     with_stats: bool):
+    """Shared body of mc_dropout_votes / mc_dropout_stats (CPU tensors out).
+
+    Returns ``(votes int32 [N, C], mean_probs float64 [N, C] | None,
+    mean_entropy float64 [N] | None)``. The logits are float32 (``scale``
+    applied once after the sum, then the bias); the statistics are computed
+    from those float32 logits in float64.
+    """
+    n, d = feats.shape
+    c = weight.shape[0]
+    S = int(num_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"num_samples must be in [1, 65535], got {S}")
+    if row_offset < 0 or row_offset + n > 2 ** 32:
+        raise ValueError("rows must satisfy row_offset + N <= 2^32")
+    thresh = dropout_threshold(p)
+    scale = dropout_scale(p)
+    f = feats.detach().float().cpu()
+    wt = weight.detach().float().cpu().t().contiguous()
+    b = bias.detach().float().cpu()
+    votes = torch.zeros(n, c, dtype=torch.int32)
+    mean_probs = torch.zeros(n, c, dtype=torch.float64) if with_stats else None
+    mean_entropy = torch.zeros(n, dtype=torch.float64) if with_stats else None
+    rows = max(1, _MCD_MAX_MASK_ELEMS // max(1, S * d))
+    ones = torch.ones(1, dtype=torch.int32)
+    cls = torch.arange(c, dtype=torch.int64)
+    for s0 in range(0, n, rows):
+        fb = f[s0 : s0 + rows]
+        nb = fb.shape[0]
+        keep = dropout_words(seed, S, nb, d, row_offset + s0) >= thresh
+        sums = torch.matmul(keep.to(torch.float32) * fb[None], wt)  # [S,nb,C]
+        logits = scale * sums + b
+        # first maximal index (torch.argmax does not promise one on ties)
+        is_max = logits == logits.max(dim=2, keepdim=True).values
+        best = torch.where(is_max, cls, c).min(dim=2).values  # [S, nb]
+        best.clamp_(max=c - 1)  # NaN logits match nothing; keep the index valid
+        votes[s0 : s0 + nb].scatter_add_(
+            1, best.t().contiguous(), ones.expand(nb, S)
+        )
+        if with_stats:
+            v = logits.double()
+            v = v - v.max(dim=2, keepdim=True).values
+            e = torch.exp(v)
+            z = e.sum(dim=2, keepdim=True)
+            probs = e / z
+            # H = log Z - sum_c p_c (v_c - max); 0 * finite = 0 where p == 0
+            ent = torch.log(z.squeeze(2)) - (probs * v).sum(dim=2)  # [S, nb]
+            mean_probs[s0 : s0 + nb] = probs.mean(dim=0)
+            mean_entropy[s0 : s0 + nb] = ent.mean(dim=0)
+    return votes, mean_probs, mean_entropy
+
+
 def mc_dropout_votes(
     feats: torch.Tensor,
     weight: torch.Tensor,
@@ -306,37 +359,45 @@ def mc_dropout_votes(
     (votes of a row with NaN/inf logits are unspecified). Rows are processed
     in chunks so only ``_MCD_MAX_MASK_ELEMS`` mask elements exist at a time.
     """
-    n, d = feats.shape
-    c = weight.shape[0]
-    S = int(num_samples)
-    if not 1 <= S <= 65535:
-        raise ValueError(f"num_samples must be in [1, 65535], got {S}")
-    if row_offset < 0 or row_offset + n > 2 ** 32:
-        raise ValueError("rows must satisfy row_offset + N <= 2^32")
-    thresh = dropout_threshold(p)
-    scale = dropout_scale(p)
+    votes, _, _ = _mc_dropout_eval(
+        feats, weight, bias, p, num_samples, seed, row_offset, with_stats=False
+    )
+    return votes.to(feats.device)
+
+
+def _mc_dropout_stats_f64(
+    feats, weight, bias, p, num_samples, seed, row_offset=0
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(votes int32, mean_probs float64, mean_entropy float64) on the CPU:
+    the unrounded values behind :func:`mc_dropout_stats`, for tests."""
+    return _mc_dropout_eval(
+        feats, weight, bias, p, num_samples, seed, row_offset, with_stats=True
+    )
+
+
+def mc_dropout_stats(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Votes, mean softmax and mean per-sample entropy of the masked heads.
+
+    Returns ``(votes int32 [N, C], mean_probs float32 [N, C], mean_entropy
+    float32 [N])``. The float32 logits are those of :func:`mc_dropout_votes`
+    (so are the votes); softmax, entropy (natural log, ``p log p = 0`` at
+    ``p = 0``) and the two means over the samples are evaluated from them in
+    float64 and rounded to float32 once at the end. Same row chunking as
+    :func:`mc_dropout_votes`.
+    """
+    votes, mean_probs, mean_entropy = _mc_dropout_stats_f64(
+        feats, weight, bias, p, num_samples, seed, row_offset
+    )
     dev = feats.device
-    f = feats.detach().float().cpu()
-    wt = weight.detach().float().cpu().t().contiguous()
-    b = bias.detach().float().cpu()
-    votes = torch.zeros(n, c, dtype=torch.int32)
-    rows = max(1, _MCD_MAX_MASK_ELEMS // max(1, S * d))
-    ones = torch.ones(1, dtype=torch.int32)
-    cls = torch.arange(c, dtype=torch.int64)
-    for s0 in range(0, n, rows):
-        fb = f[s0 : s0 + rows]
-        nb = fb.shape[0]
-        keep = dropout_words(seed, S, nb, d, row_offset + s0) >= thresh
-        sums = torch.matmul(keep.to(torch.float32) * fb[None], wt)  # [S,nb,C]
-        logits = scale * sums + b
-        # first maximal index (torch.argmax does not promise one on ties)
-        is_max = logits == logits.max(dim=2, keepdim=True).values
-        best = torch.where(is_max, cls, c).min(dim=2).values  # [S, nb]
-        best.clamp_(max=c - 1)  # NaN logits match nothing; keep the index valid
-        votes[s0 : s0 + nb].scatter_add_(
-            1, best.t().contiguous(), ones.expand(nb, S)
-        )
-    return votes.to(dev)
+    return votes.to(dev), mean_probs.float().to(dev), mean_entropy.float().to(dev)
 
 
 # ---------------------------------------------------------------------------

@@ -64,6 +64,10 @@ void launch_stem(int, const short*, short*, const short*, const float*,
 void launch_mc_dropout_votes(const float*, const float*, const float*, int,
                              int, int, int, uint32_t, float, uint32_t,
                              uint32_t, uint32_t, int*, hipStream_t);
+void launch_mc_dropout_stats(const float*, const float*, const float*, int,
+                             int, int, int, uint32_t, float, uint32_t,
+                             uint32_t, uint32_t, int*, float*, float*,
+                             hipStream_t);
 int mc_dropout_max_grid(int, int);
 int mc_dropout_rows_per_block();
 int mc_dropout_max_classes();
@@ -499,11 +503,11 @@ torch::Tensor resnet_stem(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
 
 // thresh = floor(p * 2^32) and scale = float32(1 / (1 - p)) are computed once
 // by the Python wrapper so the CPU oracle and the kernel share the exact bits.
-torch::Tensor mc_dropout_votes(torch::Tensor feats, torch::Tensor weight,
-                               torch::Tensor bias, int64_t thresh,
-                               double scale, int64_t num_samples,
-                               int64_t seed_lo, int64_t seed_hi,
-                               int64_t row_offset) {
+// Argument checks shared by mc_dropout_votes and mc_dropout_stats.
+static void mc_dropout_check(const torch::Tensor& feats,
+                             const torch::Tensor& weight,
+                             const torch::Tensor& bias, int64_t thresh,
+                             int64_t num_samples, int64_t row_offset) {
   check_f32_2d(feats, "feats");
   check_f32_2d(weight, "weight");
   TORCH_CHECK(bias.is_cuda() && bias.dtype() == torch::kFloat32 &&
@@ -521,6 +525,15 @@ torch::Tensor mc_dropout_votes(torch::Tensor feats, torch::Tensor weight,
   TORCH_CHECK(n <= 0x7FFFFFFFll && row_offset >= 0 &&
                   row_offset + n <= 0x100000000ll,
               "rows must satisfy row_offset + N <= 2^32");
+}
+
+torch::Tensor mc_dropout_votes(torch::Tensor feats, torch::Tensor weight,
+                               torch::Tensor bias, int64_t thresh,
+                               double scale, int64_t num_samples,
+                               int64_t seed_lo, int64_t seed_hi,
+                               int64_t row_offset) {
+  mc_dropout_check(feats, weight, bias, thresh, num_samples, row_offset);
+  const int64_t n = feats.size(0), d = feats.size(1), c = weight.size(0);
   auto votes = torch::empty({n, c}, feats.options().dtype(torch::kInt32));
   if (n == 0) return votes;
   launch_mc_dropout_votes(
@@ -529,6 +542,28 @@ torch::Tensor mc_dropout_votes(torch::Tensor feats, torch::Tensor weight,
       (uint32_t)thresh, (float)scale, (uint32_t)seed_lo, (uint32_t)seed_hi,
       (uint32_t)row_offset, votes.data_ptr<int>(), cur_stream());
   return votes;
+}
+
+// votes as above plus the mean softmax [N, C] and the mean per-sample
+// entropy [N] of the same S masked heads, from one launch.
+std::vector<torch::Tensor> mc_dropout_stats(
+    torch::Tensor feats, torch::Tensor weight, torch::Tensor bias,
+    int64_t thresh, double scale, int64_t num_samples, int64_t seed_lo,
+    int64_t seed_hi, int64_t row_offset) {
+  mc_dropout_check(feats, weight, bias, thresh, num_samples, row_offset);
+  const int64_t n = feats.size(0), d = feats.size(1), c = weight.size(0);
+  auto votes = torch::empty({n, c}, feats.options().dtype(torch::kInt32));
+  auto mean_probs = torch::empty({n, c}, feats.options());
+  auto mean_entropy = torch::empty({n}, feats.options());
+  if (n == 0) return {votes, mean_probs, mean_entropy};
+  launch_mc_dropout_stats(
+      feats.data_ptr<float>(), weight.data_ptr<float>(),
+      bias.data_ptr<float>(), (int)n, (int)d, (int)c, (int)num_samples,
+      (uint32_t)thresh, (float)scale, (uint32_t)seed_lo, (uint32_t)seed_hi,
+      (uint32_t)row_offset, votes.data_ptr<int>(),
+      mean_probs.data_ptr<float>(), mean_entropy.data_ptr<float>(),
+      cur_stream());
+  return {votes, mean_probs, mean_entropy};
 }
 
 }  // namespace
@@ -557,6 +592,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resnet_down", &resnet_down);
   m.def("resnet_stem", &resnet_stem);
   m.def("mc_dropout_votes", &mc_dropout_votes);
+  m.def("mc_dropout_stats", &mc_dropout_stats);
   m.def("mc_dropout_max_grid", &mc_dropout_max_grid);
   m.def("mc_dropout_rows_per_block", &mc_dropout_rows_per_block);
   m.def("mc_dropout_max_classes", &mc_dropout_max_classes);

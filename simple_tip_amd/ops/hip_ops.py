@@ -113,15 +113,8 @@ def mc_dropout_check_envelope(C: int, D: int) -> None:
         )
 
 
-def mc_dropout_votes(
-    feats: torch.Tensor,
-    weight: torch.Tensor,
-    bias: torch.Tensor,
-    p: float,
-    num_samples: int,
-    seed: int,
-    row_offset: int = 0,
-) -> torch.Tensor:
+def _mc_dropout_args(feats, weight, bias, p, num_samples, seed, row_offset):
+    """Validate and convert the arguments shared by the two mcdropout ops."""
     from . import fallback
 
     if feats.dim() != 2 or weight.dim() != 2 or bias.dim() != 1:
@@ -139,7 +132,7 @@ def mc_dropout_votes(
         raise ValueError("rows must satisfy row_offset + N <= 2^32")
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     dev = feats.device
-    return _ext.mc_dropout_votes(
+    return (
         feats.float().contiguous(),
         weight.to(dev).float().contiguous(),
         bias.to(dev).float().contiguous(),
@@ -150,6 +143,35 @@ def mc_dropout_votes(
         seed >> 32,
         row_offset,
     )
+
+
+def mc_dropout_votes(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> torch.Tensor:
+    return _ext.mc_dropout_votes(
+        *_mc_dropout_args(feats, weight, bias, p, num_samples, seed, row_offset)
+    )
+
+
+def mc_dropout_stats(
+    feats: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    p: float,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    votes, mean_probs, mean_entropy = _ext.mc_dropout_stats(
+        *_mc_dropout_args(feats, weight, bias, p, num_samples, seed, row_offset)
+    )
+    return votes, mean_probs, mean_entropy
 
 
 def _empty(t):
