@@ -25,6 +25,7 @@ setup(
             sources=[
                 os.path.join(HIP_DIR, "bindings.cpp"),
                 os.path.join(HIP_DIR, "pairwise.hip"),
+                os.path.join(HIP_DIR, "segment.hip"),
                 os.path.join(HIP_DIR, "coverage.hip"),
                 os.path.join(HIP_DIR, "cam.hip"),
                 os.path.join(HIP_DIR, "resnet_fused.hip"),

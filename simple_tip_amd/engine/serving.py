@@ -9,6 +9,11 @@ kernels: the batch is class-sorted once, padded to 128-row segments, and a
 SINGLE kernel launch covers every class for DSA (and one for LSA), cutting
 the host op count per batch to ~40.
 
+In bf16 mode the sort-and-pad itself moves to the device (the sync-free path
+below): a plan kernel writes the padded-row -> source-row map and the
+kernels gather through it, ~10 launches per batch with no host<->device
+copy, so the host can queue the next forward while a batch is still scoring.
+
 Numerics: the fp32 mode is identical to the per-class path (same kernels,
 same fp32 accumulation, same tie rules; tests/test_gpu_serving.py asserts
 equality). The optional bf16 mode (``pairwise_dtype=torch.bfloat16``) uses
@@ -16,6 +21,7 @@ the bf16-operand MFMA kernels — 4.6x faster, scores shift only by operand
 rounding (rank correlation > 0.99 vs fp32, pinned by test).
 """
 
+import os
 from typing import Optional, Tuple
 
 import numpy as np
@@ -43,6 +49,7 @@ class FusedPrioritizer:
         lsa: Optional[MultiModalSA],
         device,
         pairwise_dtype=None,
+        fast: Optional[bool] = None,
     ):
         self.ext = _load_compiled()
         self.device = device
@@ -190,6 +197,150 @@ class FusedPrioritizer:
                 )
                 self.lsa_ready = True
 
+        self.fast = (
+            fast is not False
+            and os.environ.get("TIP_NO_FAST_SCORING") != "1"
+            and self._fast_eligible(lsa)
+        )
+        if self.fast:
+            self._build_fast_tables()
+
+    # ------------------------------------------------------------------
+    # Sync-free path: device segment plan + gathered kernels. The batch is
+    # never class-sorted or padded in memory; a plan kernel writes the
+    # padded-row -> source-row map, the pairwise / whiten kernels gather
+    # source rows through it and the combine kernels scatter the final
+    # scores back, so a call is ~9 launches with no host<->device copy and
+    # no host loop over classes (docs/kernels.md, "grouped scoring,
+    # sync-free path").
+    # ------------------------------------------------------------------
+
+    def _fast_eligible(self, lsa) -> bool:
+        if not self.bf16 or self.shard_train:
+            return False
+        if torch.device(self.device).type != "cuda":
+            return False
+        if self.trainS.shape[1] % 8 != 0:
+            return False
+        if self.num_classes > 256:
+            return False
+        if lsa is not None and any(m[0] == "fallback" for m in self.lsa_mode):
+            return False
+        if self.lsa_ready and self.lsa_d > self.ext.grouped_whiten_max_features():
+            return False
+        return True
+
+    def _build_fast_tables(self):
+        dev, c = self.device, self.num_classes
+        self._ws = {}
+        self._plan_event = None
+        if not self.lsa_ready:
+            return
+        d = self.lsa_d
+        keep = np.zeros((c, d), dtype=np.int32)
+        # per-class matrices zero-padded to [pad16(d), pad32(d)]: aligned
+        # 16-byte fragment loads, no tail handling in the kernel
+        wt = torch.zeros(
+            c, (d + 15) // 16 * 16, (d + 31) // 32 * 32,
+            dtype=torch.bfloat16, device=dev,
+        )
+        fused = np.zeros(c, dtype=np.int32)
+        const = self.lsa_consts.cpu().numpy().astype(np.float32).copy()
+        for cls, mode in enumerate(self.lsa_mode):
+            if mode[0] == "fused":
+                _, kidx, linv_t = mode
+                keep[cls] = (
+                    kidx.cpu().numpy() if kidx is not None else np.arange(d)
+                )
+                # K-contiguous per output column: wt[c, n, k] = linv_t[k, n]
+                wt[cls, :d, :d] = linv_t.t()
+                fused[cls] = 1
+            else:
+                const[cls] = mode[1]
+        self._keep_cols = int(keep.max()) + 1  # widest source column read
+        self.lsa_keep = torch.from_numpy(keep).to(dev)
+        self.lsa_wt = wt.contiguous()
+        self.lsa_cls_fused = torch.from_numpy(fused).to(dev)
+        self.lsa_cls_const = torch.from_numpy(const).to(dev)
+
+    def _workspaces(self, b: int, d_at: int):
+        """Per-(B, D) scratch, reused from call to call: each call ends with
+        the main stream waiting on the LSA stream, so the next call's
+        kernels are ordered after every reader. Nothing read into an output
+        depends on what a previous call left here."""
+        ws = self._ws.get((b, d_at))
+        if ws is not None:
+            return ws
+        if len(self._ws) >= 4:
+            self._ws.clear()
+        dev, c = self.device, self.num_classes
+        bp = self.ext.segment_plan_rows(b, c)
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = {
+            "tseg": torch.empty(c + 1, **i32),
+            "rowmap": torch.empty(bp, **i32),
+            "dest": torch.empty(b, **i32),
+            "an": torch.empty(b, **f32),
+            "pval": torch.empty(self.jb_max, bp, **f32),
+            "pidx": torch.empty(self.jb_max, bp, **i32),
+            "dist": torch.empty(b, **f32),
+            "idx": torch.empty(b, **i32),
+        }
+        if self.lsa_ready:
+            ws["white"] = torch.empty(
+                bp, self.lsa_d, dtype=torch.bfloat16, device=dev
+            )
+            ws["wan"] = torch.empty(bp, **f32)
+            ws["pkde"] = torch.empty(self.lsa_jb_max, bp, 2, **f32)
+        self._ws[(b, d_at)] = ws
+        return ws
+
+    def _fast_call(self, ats, pred):
+        b, d_at = ats.shape
+        assert d_at == self.trainS16.shape[1], "AT width differs from the fit"
+        ext, ws = self.ext, self._workspaces(b, d_at)
+        a16 = ats.to(torch.bfloat16).contiguous()  # no-op for bf16 ATs
+        pred = pred.to(torch.int64).contiguous()
+        ext.segment_plan_out(
+            pred, self.num_classes, ws["tseg"], ws["rowmap"], ws["dest"]
+        )
+        ext.rownorm_bf16_out(a16, ws["an"])
+        # unplaced rows (prediction outside the fitted range) stay +inf
+        out = torch.full(
+            (2, b), float("inf"), dtype=torch.float32, device=ats.device
+        )
+        main_stream = torch.cuda.current_stream()
+        if self.lsa_ready:
+            assert self._keep_cols <= d_at
+            if not hasattr(self, "_lsa_stream"):
+                self._lsa_stream = torch.cuda.Stream()
+            if self._plan_event is None:
+                self._plan_event = torch.cuda.Event()
+            self._plan_event.record(main_stream)
+            with torch.cuda.stream(self._lsa_stream):
+                self._lsa_stream.wait_event(self._plan_event)
+                ext.grouped_whiten_bf16(
+                    a16, ws["rowmap"], ws["tseg"], self.lsa_nseg,
+                    self.lsa_keep, self.lsa_wt, ws["white"],
+                )
+                ext.rownorm_bf16_out(ws["white"], ws["wan"], ws["tseg"])
+                ext.grouped_kde_plan(
+                    ws["white"], self.lsa_wtrainS16, ws["tseg"],
+                    self.lsa_nseg, ws["rowmap"], ws["wan"],
+                    self.lsa_wnormS16, self.lsa_cls_fused,
+                    self.lsa_cls_const, self.lsa_jb_max, ws["pkde"], out[1],
+                )
+        ext.grouped_rowmin_plan(
+            a16, self.trainS16, ws["tseg"], self.nseg, ws["rowmap"],
+            ws["an"], self.bnormS16, self.btableS, self.jb_max,
+            ws["pval"], ws["pidx"], out[0], ws["dist"], ws["idx"],
+        )
+        if self.lsa_ready:
+            main_stream.wait_stream(self._lsa_stream)
+            return out[0], out[1]
+        return out[0], None
+
     def _lsa_lse(self, padded, bp, tseg_cpu, tseg):
         """Per-class whiten GEMMs + one grouped KDE launch (+ cross-rank
         logsumexp merge of the train-shard partials in shard mode).
@@ -261,6 +412,8 @@ class FusedPrioritizer:
         self, ats: torch.Tensor, pred: torch.Tensor
     ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """(dsa scores, lsa scores or None) for fp32 ATs [B, D] on device."""
+        if self.fast and ats.is_cuda:
+            return self._fast_call(ats, pred)
         b = ats.shape[0]
         order, dest, tseg_cpu, tseg = self._segment(ats, pred)
         bp = int(tseg_cpu[-1])

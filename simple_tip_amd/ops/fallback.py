@@ -479,3 +479,52 @@ def bucketize_profile(values: torch.Tensor, thresholds: torch.Tensor) -> torch.T
     rows = torch.nonzero(valid, as_tuple=True)[0]
     prof[rows, idx[valid]] = True
     return pack_bits(prof).to(values.device)
+
+
+# ---------------------------------------------------------------------------
+# Segment plan (sync-free grouped scoring)
+# ---------------------------------------------------------------------------
+
+SEGMENT_ROWS = 128
+
+
+def segment_plan_rows(batch: int, num_classes: int) -> int:
+    """Static bound on the sum of the 128-padded class counts."""
+    return SEGMENT_ROWS * ((batch + SEGMENT_ROWS - 1) // SEGMENT_ROWS + num_classes)
+
+
+def segment_plan(
+    pred: torch.Tensor, num_classes: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Class-sorted, 128-padded layout of a batch as an index plan.
+
+    Returns ``(tseg int32[C+1], rowmap int32[bp_max], dest int32[B])``:
+    ``tseg`` are the padded segment offsets, ``rowmap[p]`` the input row at
+    padded row ``p`` (-1 for pad rows and rows >= ``tseg[C]``) and ``dest[i]``
+    the padded row of input ``i``. Inside a class inputs keep ascending
+    index order (stable sort). A prediction outside ``[0, C)`` gets
+    ``dest = -1`` and appears nowhere in ``rowmap``. Reference for the HIP
+    ``segment_plan`` kernel, which must equal it exactly.
+    """
+    assert pred.dim() == 1
+    p = pred.to(torch.int64)
+    b = p.shape[0]
+    valid = (p >= 0) & (p < num_classes)
+    counts = torch.bincount(p[valid], minlength=num_classes)
+    padded = (counts + SEGMENT_ROWS - 1) // SEGMENT_ROWS * SEGMENT_ROWS
+    tseg = torch.zeros(num_classes + 1, dtype=torch.int64, device=p.device)
+    tseg[1:] = torch.cumsum(padded, 0)
+    starts = torch.zeros(num_classes, dtype=torch.int64, device=p.device)
+    starts[1:] = torch.cumsum(counts, 0)[:-1]
+    rows = torch.nonzero(valid, as_tuple=True)[0]
+    order = rows[torch.argsort(p[rows], stable=True)]
+    cls = p[order]
+    intra = torch.arange(order.shape[0], device=p.device) - starts[cls]
+    where = tseg[cls] + intra
+    rowmap = torch.full(
+        (segment_plan_rows(b, num_classes),), -1, dtype=torch.int32, device=p.device
+    )
+    rowmap[where] = order.to(torch.int32)
+    dest = torch.full((b,), -1, dtype=torch.int32, device=p.device)
+    dest[order] = where.to(torch.int32)
+    return tseg.to(torch.int32), rowmap, dest

@@ -68,6 +68,24 @@ void launch_mc_dropout_stats(const float*, const float*, const float*, int,
                              int, int, int, uint32_t, float, uint32_t,
                              uint32_t, uint32_t, int*, float*, float*,
                              hipStream_t);
+int segment_plan_max_classes();
+void launch_segment_plan(const int64_t*, int, int, int, int*, int*, int*,
+                         hipStream_t);
+void launch_rownorm_bf16(const short*, int, int, const int*, float*,
+                         hipStream_t);
+int grouped_whiten_max_features();
+void launch_grouped_whiten_bf16(const short*, int, int, const int*, const int*,
+                                const int*, int, const int*, const short*, int,
+                                int, int, int, short*, hipStream_t);
+void launch_grouped_rowmin_plan(const short*, int, const short*, const float*,
+                                const float*, const int*, const int*,
+                                const int*, const float*, int, int, int, int,
+                                float*, int*, float*, float*, int*,
+                                hipStream_t);
+void launch_grouped_kde_plan(const short*, const short*, const float*,
+                             const float*, const int*, const int*, const int*,
+                             int, const int*, const float*, int, int, int, int,
+                             float2*, float*, hipStream_t);
 int mc_dropout_max_grid(int, int);
 int mc_dropout_rows_per_block();
 int mc_dropout_max_classes();
@@ -217,6 +235,166 @@ torch::Tensor grouped_kde_bf16(torch::Tensor testWS, torch::Tensor trainWS,
       reinterpret_cast<float2*>(pkde.data_ptr<float>()),
       out.data_ptr<float>(), cur_stream());
   return out;
+}
+
+// ---- sync-free grouped scoring (segment plan + gathered kernels) ----
+// Every function below writes into caller-owned workspaces and enqueues on
+// the current stream only: no allocation-dependent sizes, no host copies.
+
+int64_t segment_plan_rows(int64_t b, int64_t c) {
+  return 128 * ((b + 127) / 128 + c);
+}
+
+void check_dev(const torch::Tensor& t, torch::ScalarType dt, int64_t numel,
+               const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name,
+              " must be a contiguous GPU tensor");
+  TORCH_CHECK(t.scalar_type() == dt, name, " has the wrong dtype");
+  TORCH_CHECK(t.numel() == numel, name, " has ", t.numel(),
+              " elements, expected ", numel);
+}
+
+const short* bf16_ptr(const torch::Tensor& t);  // defined below
+
+void segment_plan_out(torch::Tensor pred, int64_t nclasses, torch::Tensor tseg,
+                      torch::Tensor rowmap, torch::Tensor dest) {
+  TORCH_CHECK(pred.dim() == 1, "pred must be 1D");
+  TORCH_CHECK(nclasses >= 1 && nclasses <= segment_plan_max_classes(),
+              "segment_plan supports 1..", segment_plan_max_classes(),
+              " classes");
+  const int64_t b = pred.size(0);
+  TORCH_CHECK(b >= 1 && b < (1 << 30), "bad batch size");
+  check_dev(pred, torch::kInt64, b, "pred");
+  check_dev(tseg, torch::kInt32, nclasses + 1, "tseg");
+  check_dev(rowmap, torch::kInt32, segment_plan_rows(b, nclasses), "rowmap");
+  check_dev(dest, torch::kInt32, b, "dest");
+  launch_segment_plan(pred.data_ptr<int64_t>(), b, nclasses, rowmap.numel(),
+                      tseg.data_ptr<int>(), rowmap.data_ptr<int>(),
+                      dest.data_ptr<int>(), cur_stream());
+}
+
+std::vector<torch::Tensor> segment_plan(torch::Tensor pred, int64_t nclasses) {
+  TORCH_CHECK(pred.is_cuda() && pred.dim() == 1, "pred must be 1D on GPU");
+  auto iopts = pred.options().dtype(torch::kInt32);
+  auto tseg = torch::empty({nclasses + 1}, iopts);
+  auto rowmap = torch::empty({segment_plan_rows(pred.size(0), nclasses)}, iopts);
+  auto dest = torch::empty({pred.size(0)}, iopts);
+  segment_plan_out(pred, nclasses, tseg, rowmap, dest);
+  return {tseg, rowmap, dest};
+}
+
+// fp32 squared norms of bf16 rows. With `tseg`, rows at or past its last
+// entry (the end of the last segment) are skipped.
+void rownorm_bf16_out(torch::Tensor x, torch::Tensor out,
+                      c10::optional<torch::Tensor> tseg) {
+  TORCH_CHECK(x.dim() == 2, "x must be 2D");
+  check_dev(x, torch::kBFloat16, x.numel(), "x");
+  check_dev(out, torch::kFloat32, x.size(0), "out");
+  const int* limit = nullptr;
+  if (tseg.has_value()) {
+    check_dev(tseg.value(), torch::kInt32, tseg.value().numel(), "tseg");
+    TORCH_CHECK(tseg.value().numel() >= 1);
+    limit = tseg.value().data_ptr<int>() + tseg.value().numel() - 1;
+  }
+  launch_rownorm_bf16(bf16_ptr(x), x.size(0), x.size(1), limit,
+                      out.data_ptr<float>(), cur_stream());
+}
+
+void grouped_whiten_bf16(torch::Tensor ats, torch::Tensor rowmap,
+                         torch::Tensor tseg, torch::Tensor wseg,
+                         torch::Tensor keep, torch::Tensor wt,
+                         torch::Tensor white) {
+  TORCH_CHECK(ats.dim() == 2 && keep.dim() == 2 && wt.dim() == 3);
+  const int64_t b = ats.size(0), dfull = ats.size(1);
+  const int64_t c = keep.size(0), d = keep.size(1);
+  const int64_t bp = segment_plan_rows(b, c);
+  check_dev(ats, torch::kBFloat16, b * dfull, "ats");
+  check_dev(rowmap, torch::kInt32, bp, "rowmap");
+  check_dev(tseg, torch::kInt32, c + 1, "tseg");
+  check_dev(wseg, torch::kInt32, c + 1, "wseg");
+  check_dev(keep, torch::kInt32, c * d, "keep");
+  // wt is [C, NP, KP]: out columns padded to 16, K padded to 32, zero-filled
+  const int64_t np = wt.size(1), kp = wt.size(2);
+  TORCH_CHECK(wt.size(0) == c && np % 16 == 0 && kp % 32 == 0 && np >= d &&
+                  np < d + 16 && kp >= d && kp < d + 32,
+              "wt must be [C, pad16(d), pad32(d)]");
+  TORCH_CHECK(d >= 1 && kp <= grouped_whiten_max_features(),
+              "grouped_whiten_bf16 supports up to ",
+              grouped_whiten_max_features(), " features");
+  check_dev(wt, torch::kBFloat16, c * np * kp, "wt");
+  check_dev(white, torch::kBFloat16, bp * d, "white");
+  launch_grouped_whiten_bf16(
+      bf16_ptr(ats), b, dfull, rowmap.data_ptr<int>(), tseg.data_ptr<int>(),
+      wseg.data_ptr<int>(), c, keep.data_ptr<int>(), bf16_ptr(wt), d, np, kp,
+      bp, reinterpret_cast<short*>(white.data_ptr()), cur_stream());
+}
+
+void grouped_rowmin_plan(torch::Tensor ats, torch::Tensor trainS,
+                         torch::Tensor tseg, torch::Tensor nseg,
+                         torch::Tensor rowmap, torch::Tensor anorm,
+                         torch::Tensor bnorm, torch::Tensor btable,
+                         int64_t jb_max, torch::Tensor pval,
+                         torch::Tensor pidx, torch::Tensor out_dsa,
+                         torch::Tensor out_dist, torch::Tensor out_idx) {
+  TORCH_CHECK(ats.dim() == 2 && trainS.dim() == 2 &&
+              ats.size(1) == trainS.size(1), "feature dims differ");
+  const int64_t b = ats.size(0), k = ats.size(1), n = trainS.size(0);
+  const int64_t c = tseg.numel() - 1;
+  const int64_t bp = segment_plan_rows(b, c);
+  TORCH_CHECK(jb_max >= 1 && k % 8 == 0, "AT width must be a multiple of 8");
+  check_dev(ats, torch::kBFloat16, b * k, "ats");
+  check_dev(trainS, torch::kBFloat16, n * k, "trainS");
+  check_dev(tseg, torch::kInt32, c + 1, "tseg");
+  check_dev(nseg, torch::kInt32, c + 1, "nseg");
+  check_dev(rowmap, torch::kInt32, bp, "rowmap");
+  check_dev(anorm, torch::kFloat32, b, "anorm");
+  check_dev(bnorm, torch::kFloat32, n, "bnorm");
+  check_dev(btable, torch::kFloat32, n, "btable");
+  check_dev(pval, torch::kFloat32, jb_max * bp, "pval");
+  check_dev(pidx, torch::kInt32, jb_max * bp, "pidx");
+  check_dev(out_dsa, torch::kFloat32, b, "out_dsa");
+  check_dev(out_dist, torch::kFloat32, b, "out_dist");
+  check_dev(out_idx, torch::kInt32, b, "out_idx");
+  launch_grouped_rowmin_plan(
+      bf16_ptr(ats), b, bf16_ptr(trainS), anorm.data_ptr<float>(),
+      bnorm.data_ptr<float>(), tseg.data_ptr<int>(), nseg.data_ptr<int>(),
+      rowmap.data_ptr<int>(), btable.data_ptr<float>(), c, bp, k, jb_max,
+      pval.data_ptr<float>(), pidx.data_ptr<int>(),
+      out_dsa.data_ptr<float>(), out_dist.data_ptr<float>(),
+      out_idx.data_ptr<int>(), cur_stream());
+}
+
+void grouped_kde_plan(torch::Tensor white, torch::Tensor wtrain,
+                      torch::Tensor tseg, torch::Tensor wseg,
+                      torch::Tensor rowmap, torch::Tensor wanorm,
+                      torch::Tensor wbnorm, torch::Tensor cls_fused,
+                      torch::Tensor cls_const, int64_t jb_max,
+                      torch::Tensor pkde, torch::Tensor out_lsa) {
+  TORCH_CHECK(white.dim() == 2 && wtrain.dim() == 2 &&
+              white.size(1) == wtrain.size(1), "feature dims differ");
+  const int64_t bp = white.size(0), d = white.size(1), n = wtrain.size(0);
+  const int64_t c = tseg.numel() - 1;
+  const int64_t b = out_lsa.numel();
+  TORCH_CHECK(jb_max >= 1 && bp == segment_plan_rows(b, c),
+              "white does not match the plan");
+  check_dev(white, torch::kBFloat16, bp * d, "white");
+  check_dev(wtrain, torch::kBFloat16, n * d, "wtrain");
+  check_dev(tseg, torch::kInt32, c + 1, "tseg");
+  check_dev(wseg, torch::kInt32, c + 1, "wseg");
+  check_dev(rowmap, torch::kInt32, bp, "rowmap");
+  check_dev(wanorm, torch::kFloat32, bp, "wanorm");
+  check_dev(wbnorm, torch::kFloat32, n, "wbnorm");
+  check_dev(cls_fused, torch::kInt32, c, "cls_fused");
+  check_dev(cls_const, torch::kFloat32, c, "cls_const");
+  check_dev(pkde, torch::kFloat32, jb_max * bp * 2, "pkde");
+  check_dev(out_lsa, torch::kFloat32, b, "out_lsa");
+  launch_grouped_kde_plan(
+      bf16_ptr(white), bf16_ptr(wtrain), wanorm.data_ptr<float>(),
+      wbnorm.data_ptr<float>(), tseg.data_ptr<int>(), wseg.data_ptr<int>(),
+      rowmap.data_ptr<int>(), b, cls_fused.data_ptr<int>(),
+      cls_const.data_ptr<float>(), c, bp, d, jb_max,
+      reinterpret_cast<float2*>(pkde.data_ptr<float>()),
+      out_lsa.data_ptr<float>(), cur_stream());
 }
 
 torch::Tensor kde_logsumexp(torch::Tensor test, torch::Tensor train) {
@@ -579,6 +757,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_kde", &grouped_kde);
   m.def("grouped_rowmin_bf16", &grouped_rowmin_bf16);
   m.def("grouped_kde_bf16", &grouped_kde_bf16);
+  m.def("segment_plan", &segment_plan);
+  m.def("segment_plan_out", &segment_plan_out);
+  m.def("segment_plan_rows", &segment_plan_rows);
+  m.def("rownorm_bf16_out", &rownorm_bf16_out, py::arg("x"), py::arg("out"),
+        py::arg("tseg") = py::none());
+  m.def("grouped_whiten_bf16", &grouped_whiten_bf16);
+  m.def("grouped_whiten_max_features", &grouped_whiten_max_features);
+  m.def("grouped_rowmin_plan", &grouped_rowmin_plan);
+  m.def("grouped_kde_plan", &grouped_kde_plan);
   m.def("profile", &profile);
   m.def("pack_bits", &pack_bits);
   m.def("popcount_rows", &popcount_rows);

@@ -457,6 +457,79 @@ __global__ void grouped_kde_combine_kernel(
   out_lse[i] = (ss > 0.f) ? (mm + __logf(ss)) : -FLT_MAX;
 }
 
+// Plan-driven combines (sync-free scoring path): the same fixed-order folds,
+// but each padded row p writes its FINAL score to its source row rowmap[p].
+// Pad rows and rows at or past tseg[nclasses] write nothing, so the outputs
+// (pre-filled with +inf by the caller) never see stale workspace content.
+__global__ void grouped_rowmin_final_kernel(
+    const float* __restrict__ pval, const int* __restrict__ pidx,
+    const int* __restrict__ tseg, const int* __restrict__ nseg, int nclasses,
+    int Bp, const int* __restrict__ rowmap, int out_rows,
+    const float* __restrict__ btable, float* __restrict__ out_dsa,
+    float* __restrict__ out_dist, int* __restrict__ out_idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp || i >= tseg[nclasses]) return;
+  const int src = rowmap[i];
+  if (src < 0 || src >= out_rows) return;
+  int cls = 0;
+  for (int c = 0; c < nclasses; ++c)
+    if (tseg[c] <= i) cls = c;
+  const int jcount = (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
+  MinIdx best{FLT_MAX, 0x7fffffff};
+  for (int b = 0; b < jcount; ++b)
+    best = min_idx_combine(
+        best, MinIdx{pval[(int64_t)b * Bp + i], pidx[(int64_t)b * Bp + i]});
+  if (jcount == 0) {
+    out_dsa[src] = INFINITY;
+    out_dist[src] = FLT_MAX;
+    out_idx[src] = -1;
+  } else if ((unsigned)best.i >= (unsigned)nseg[nclasses]) {
+    // every distance was NaN (non-finite activations): no argmin to gather
+    out_dsa[src] = NAN;
+    out_dist[src] = NAN;
+    out_idx[src] = -1;
+  } else {
+    const float dist = sqrtf(best.v);
+    out_dsa[src] = dist / btable[best.i];
+    out_dist[src] = dist;
+    out_idx[src] = best.i;
+  }
+}
+
+__global__ void grouped_kde_final_kernel(
+    const float2* __restrict__ pkde, const int* __restrict__ tseg,
+    const int* __restrict__ nseg, int nclasses, int Bp,
+    const int* __restrict__ rowmap, int out_rows,
+    const int* __restrict__ cls_fused,    // [C] 1: KDE class, 0: constant
+    const float* __restrict__ cls_const,  // [C] KDE constant / the score
+    float* __restrict__ out_lsa) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp || i >= tseg[nclasses]) return;
+  const int src = rowmap[i];
+  if (src < 0 || src >= out_rows) return;
+  int cls = 0;
+  for (int c = 0; c < nclasses; ++c)
+    if (tseg[c] <= i) cls = c;
+  if (!cls_fused[cls]) {
+    out_lsa[src] = cls_const[cls];
+    return;
+  }
+  const int jcount = (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
+  float mm = -FLT_MAX, ss = 0.f;
+  for (int b = 0; b < jcount; ++b) {
+    const float2 p = pkde[(int64_t)b * Bp + i];
+    if (p.y <= 0.f) continue;
+    if (p.x > mm) {
+      ss = p.y + ((ss > 0.f) ? ss * __expf(mm - p.x) : 0.f);
+      mm = p.x;
+    } else {
+      ss += p.y * __expf(p.x - mm);
+    }
+  }
+  const float lse = (ss > 0.f) ? (mm + __logf(ss)) : -FLT_MAX;
+  out_lsa[src] = -(lse + cls_const[cls]);
+}
+
 // ---------------------------------------------------------------------------
 // bf16 grouped variant (fp32 accumulate). The activation traces come out of
 // a bf16 forward, so bf16 operands lose almost nothing while the MFMA
@@ -488,20 +561,18 @@ struct BStage {
   bf16x8 v[2];
 };
 
-TIP_DEV BStage bstage_load(const short* __restrict__ src, int rows, int K,
-                           int row0, int k0) {
+// `grow` is the source row to stage and `ok` whether it exists at all.
+TIP_DEV BStage bstage_load_row(const short* __restrict__ src, int grow,
+                               bool ok, int K, int k0) {
   BStage s;
-  const int t = threadIdx.x;
-  const int r = t >> 1;
-  const int kq = (t & 1) * 16;
-  const int grow = row0 + r;
+  const int kq = (threadIdx.x & 1) * 16;
   const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int gk = k0 + kq + h * 8;
-    if (grow < rows && gk + 7 < K) {
+    if (ok && gk + 7 < K) {
       s.v[h] = *reinterpret_cast<const bf16x8*>(&src[(int64_t)grow * K + gk]);
-    } else if (grow < rows) {
+    } else if (ok) {
       bf16x8 tmp = zero;
       for (int e = 0; e < 8; ++e)
         if (gk + e < K) tmp[e] = src[(int64_t)grow * K + gk + e];
@@ -513,6 +584,12 @@ TIP_DEV BStage bstage_load(const short* __restrict__ src, int rows, int K,
   return s;
 }
 
+TIP_DEV BStage bstage_load(const short* __restrict__ src, int rows, int K,
+                           int row0, int k0) {
+  const int grow = row0 + (threadIdx.x >> 1);
+  return bstage_load_row(src, grow, grow < rows, K, k0);
+}
+
 TIP_DEV void bstage_write(short* lds, const BStage& s) {
   const int t = threadIdx.x;
   const int r = t >> 1;
@@ -521,13 +598,19 @@ TIP_DEV void bstage_write(short* lds, const BStage& s) {
   *reinterpret_cast<bf16x8*>(&lds[r * BROW + kq + 8]) = s.v[1];
 }
 
-template <int EPI>
+// GATHER: A is the UNPADDED source [a_rows, K] and padded row p reads source
+// row rowmap[p] (zeros where it is -1), its norm through the same index, so
+// no class-sorted padded copy of the batch exists; Bp is then the static row
+// bound of the plan (rows at or past tseg[nclasses] hold nothing).
+template <int EPI, bool GATHER>
 __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
     const short* __restrict__ A,      // [Bp, K] bf16, class-sorted padded
     const short* __restrict__ B,      // [Ntot, K] bf16 class-concatenated
     const float* __restrict__ anorm,  // [Bp] norms of the bf16 values
     const float* __restrict__ bnorm,  // [Ntot]
     const int* __restrict__ tseg, const int* __restrict__ nseg,
+    const int* __restrict__ rowmap,   // GATHER: [Bp] padded row -> A row
+    int a_rows,                       // GATHER: rows of A
     int nclasses, int Bp, int K,
     float* __restrict__ pmin_val, int* __restrict__ pmin_idx,
     float2* __restrict__ pkde) {
@@ -540,6 +623,8 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
   const int bi = blockIdx.y;
   const int bj = blockIdx.x;
   const int row0 = bi * BM;
+  // a row block past the last segment belongs to no class
+  if (row0 >= tseg[nclasses]) return;
   int cls = 0;
   for (int c = 0; c < nclasses; ++c)
     if (tseg[c] <= row0) cls = c;
@@ -554,8 +639,16 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
   const int fj = lane & 15;
   const int fg = lane >> 4;
 
+  // the A row this thread stages (fixed over the k loop)
+  int arow = row0 + (threadIdx.x >> 1);
+  bool arow_ok = arow < Bp;
+  if (GATHER) {
+    arow = arow_ok ? rowmap[arow] : -1;
+    arow_ok = arow >= 0 && arow < a_rows;
+  }
+
   f32x4b acc[4][4] = {};
-  BStage ra = bstage_load(A, Bp, K, row0, 0);
+  BStage ra = bstage_load_row(A, arow, arow_ok, K, 0);
   BStage rb = bstage_load(B, ncol1, K, col0, 0);
   bstage_write(As, ra);
   bstage_write(Bs, rb);
@@ -563,7 +656,7 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
   for (int k0 = 0; k0 < K; k0 += BBK) {
     const bool has_next = (k0 + BBK) < K;
     if (has_next) {
-      ra = bstage_load(A, Bp, K, row0, k0 + BBK);
+      ra = bstage_load_row(A, arow, arow_ok, K, k0 + BBK);
       rb = bstage_load(B, ncol1, K, col0, k0 + BBK);
     }
     bf16x8 af[4], bf[4];
@@ -597,7 +690,13 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
     for (int reg = 0; reg < 4; ++reg) {
       const int row_local = wr * 64 + tr * 16 + fg * 4 + reg;
       const int gi = row0 + row_local;
-      const float an = anorm[gi];
+      float an;
+      if (GATHER) {
+        const int src = rowmap[gi];
+        an = (src >= 0 && src < a_rows) ? anorm[src] : 0.f;
+      } else {
+        an = anorm[gi];
+      }
       MinIdx mi{FLT_MAX, 0x7fffffff};
       float dvals[4];
 #pragma unroll
@@ -791,8 +890,9 @@ void launch_grouped_rowmin_bf16(const short* a, const short* b,
                                 float* pval, int* pidx, float* out_dist,
                                 int64_t* out_idx, hipStream_t s) {
   dim3 grid(jb_max, ceil_div(bp, BM));
-  grouped_pairwise_bf16_kernel<EPI_ROWMIN><<<grid, 256, 0, s>>>(
-      a, b, an, bn, tseg, nseg, nclasses, bp, k, pval, pidx, nullptr);
+  grouped_pairwise_bf16_kernel<EPI_ROWMIN, false><<<grid, 256, 0, s>>>(
+      a, b, an, bn, tseg, nseg, nullptr, 0, nclasses, bp, k, pval, pidx,
+      nullptr);
   grouped_rowmin_combine_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pval, pidx, tseg, nseg, nclasses, bp, out_dist, out_idx);
 }
@@ -803,8 +903,44 @@ void launch_grouped_kde_bf16(const short* a, const short* b, const float* an,
                              int jb_max, float2* pkde, float* out_lse,
                              hipStream_t s) {
   dim3 grid(jb_max, ceil_div(bp, BM));
-  grouped_pairwise_bf16_kernel<EPI_KDE><<<grid, 256, 0, s>>>(
-      a, b, an, bn, tseg, nseg, nclasses, bp, k, nullptr, nullptr, pkde);
+  grouped_pairwise_bf16_kernel<EPI_KDE, false><<<grid, 256, 0, s>>>(
+      a, b, an, bn, tseg, nseg, nullptr, 0, nclasses, bp, k, nullptr, nullptr,
+      pkde);
   grouped_kde_combine_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pkde, tseg, nseg, nclasses, bp, out_lse);
+}
+
+// Sync-free path: A gathered through the segment plan, final DSA scores
+// written per source row.
+void launch_grouped_rowmin_plan(const short* a, int a_rows, const short* b,
+                                const float* an, const float* bn,
+                                const int* tseg, const int* nseg,
+                                const int* rowmap, const float* btable,
+                                int nclasses, int bp, int k, int jb_max,
+                                float* pval, int* pidx, float* out_dsa,
+                                float* out_dist, int* out_idx, hipStream_t s) {
+  dim3 grid(jb_max, ceil_div(bp, BM));
+  grouped_pairwise_bf16_kernel<EPI_ROWMIN, true><<<grid, 256, 0, s>>>(
+      a, b, an, bn, tseg, nseg, rowmap, a_rows, nclasses, bp, k, pval, pidx,
+      nullptr);
+  grouped_rowmin_final_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
+      pval, pidx, tseg, nseg, nclasses, bp, rowmap, a_rows, btable, out_dsa,
+      out_dist, out_idx);
+}
+
+// Sync-free path: `a` is the whitened workspace (already in padded layout),
+// final LSA scores written per source row.
+void launch_grouped_kde_plan(const short* a, const short* b, const float* an,
+                             const float* bn, const int* tseg,
+                             const int* nseg, const int* rowmap, int out_rows,
+                             const int* cls_fused, const float* cls_const,
+                             int nclasses, int bp, int k, int jb_max,
+                             float2* pkde, float* out_lsa, hipStream_t s) {
+  dim3 grid(jb_max, ceil_div(bp, BM));
+  grouped_pairwise_bf16_kernel<EPI_KDE, false><<<grid, 256, 0, s>>>(
+      a, b, an, bn, tseg, nseg, nullptr, 0, nclasses, bp, k, nullptr, nullptr,
+      pkde);
+  grouped_kde_final_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
+      pkde, tseg, nseg, nclasses, bp, rowmap, out_rows, cls_fused, cls_const,
+      out_lsa);
 }
