@@ -6,8 +6,10 @@ MIOpen-backed `forward_taps` is LAUNCH-bound for these small models
 promotes the bench-only optimisation into the engine:
 
 - BatchNorm folds into the preceding convs (exact algebra, models/fuse.py);
-- ResNet-20 routes to the hand-written fused block kernels
-  (ops/hip/resnet_fused.hip) when the extension is available;
+- ResNet-20 routes to the hand-written fused kernels (three stage-resident
+  launches, ops/hip/resnet_stages.hip; per-block kernels,
+  ops/hip/resnet_fused.hip, for inputs that are not contiguous fp32 NHWC)
+  when the extension is available;
 - the fixed-shape forward is captured ONCE into a hipGraph and replayed per
   batch — per-step launch overhead becomes one graph launch.
 

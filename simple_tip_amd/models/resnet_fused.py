@@ -1,10 +1,23 @@
 """Fused ResNet-20 inference runner (hand-written CDNA4 kernels).
 
-Wraps ops/hip/resnet_fused.hip: one kernel launch per residual block (input
-plane staged to LDS with halo, conv1 intermediate never leaves the CU),
-bf16 NHWC, MFMA 16x16x32. Weights come from a BN-folded :class:`ResNet20`
-(models/fuse.py) and are pre-packed on the host into the MFMA B-fragment
-order [cout_tiles][ksteps][64 lanes][8].
+Wraps ops/hip/resnet_fused.hip, bf16 NHWC, MFMA 16x16x32. Weights come from
+a BN-folded :class:`ResNet20` (models/fuse.py) and are pre-packed on the
+host into the MFMA B-fragment order [cout_tiles][ksteps][64 lanes][8].
+
+Two paths compute the same ATs, bit for bit:
+
+- stage-resident (3 launches): a contiguous fp32 ``[B, 32, 32, 3]`` device
+  tensor goes through ``resnet_stage1/2/3``. Each kernel keeps the
+  activation plane in LDS across its blocks; stage 1 converts the input to
+  bf16 while staging it, stage 3 also pools and applies the fc layer.
+  ``TIP_NO_STAGE_FUSED=1`` turns this path off.
+- per-block (11 launches + torch glue): stem, one launch per residual
+  block (input plane staged to LDS with halo, conv1 intermediate never
+  leaves the CU), then ``mean`` and the fc GEMM in torch. Every other input
+  (other channel counts or dtypes, strided tensors) takes this path.
+
+The logits of the two paths differ by fp32 summation order only (the stage
+path's order is fixed per row: see ``stage3_kernel``).
 
 Feature-order note: activations are NHWC, so the 4096-wide stage-3 AT is
 HWC-flattened (the torch path flattens CHW). L2/KDE/Mahalanobis scores are
@@ -12,6 +25,7 @@ invariant under any FIXED feature permutation; train and test ATs must
 simply come from the same path.
 """
 
+import os
 from typing import List, Tuple
 
 import torch
@@ -88,15 +102,47 @@ class FusedResNet20:
         self.fc_w = pool_fc.weight.detach().float().to(device)
         self.fc_b = pool_fc.bias.detach().float().to(device)
 
+        # parameter lists of the three stage kernels, in forward order
+        def flat(blks):
+            return [t.reshape(-1, 8) if t.dtype == torch.bfloat16 else t
+                    for blk in blks for t in blk[2:]]
+
+        kinds = [blk[0] for blk in self.blocks]
+        assert kinds == ["res"] * 3 + ["down"] + ["res"] * 2 + ["down"] + ["res"] * 2
+        self.stage_params = (
+            [self.stem_w.reshape(-1, 8), self.stem_b] + flat(self.blocks[:4]),
+            flat(self.blocks[4:7]),
+            flat(self.blocks[7:]) + [self.fc_w.contiguous(), self.fc_b],
+        )
+        self.stage_fused_calls = 0  # forwards that took the 3-launch path
+
     @torch.no_grad()
     def __call__(self, x_nchw: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         x = x_nchw.to(self.device, torch.float32)
         return self.forward_nhwc(x.permute(0, 2, 3, 1))
 
+    def _takes_stage_path(self, x: torch.Tensor) -> bool:
+        return (
+            os.environ.get("TIP_NO_STAGE_FUSED") != "1"
+            and x.device == self.stem_b.device
+            and x.is_cuda
+            and x.dtype == torch.float32
+            and x.dim() == 4
+            and tuple(x.shape[1:]) == (32, 32, 3)
+            and x.is_contiguous()
+            and x.data_ptr() % 16 == 0
+        )
+
     @torch.no_grad()
     def forward_nhwc(self, x_nhwc: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Forward for NHWC inputs [B, 32, 32, C<=8] (skips the 125-MB
         strided NCHW->NHWC transpose on the hot path)."""
+        if self._takes_stage_path(x_nhwc):
+            self.stage_fused_calls += 1
+            cur = self.ext.resnet_stage1(x_nhwc, self.stage_params[0])
+            cur = self.ext.resnet_stage2(cur, self.stage_params[1])
+            ats, logits = self.ext.resnet_stage3(cur, self.stage_params[2])
+            return ats, logits
         b = x_nhwc.shape[0]
         x = x_nhwc.to(self.device)
         nhwc = torch.zeros(b, 32, 32, 8, device=self.device, dtype=torch.bfloat16)

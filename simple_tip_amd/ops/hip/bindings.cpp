@@ -61,6 +61,10 @@ void launch_downblock(int, int, const short*, short*, const short*,
                       const float*, hipStream_t);
 void launch_stem(int, const short*, short*, const short*, const float*,
                  hipStream_t);
+void launch_stage1(int, const float*, short*, const void* const*, hipStream_t);
+void launch_stage2(int, const short*, short*, const void* const*, hipStream_t);
+void launch_stage3(int, const short*, short*, float*, const void* const*,
+                   hipStream_t);
 void launch_mc_dropout_votes(const float*, const float*, const float*, int,
                              int, int, int, uint32_t, float, uint32_t,
                              uint32_t, uint32_t, int*, hipStream_t);
@@ -677,6 +681,115 @@ torch::Tensor resnet_stem(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
   return out;
 }
 
+// ---- stage-resident forward: three kernels, planes stay in LDS ----
+
+// Collects a stage's parameter pointers in forward order and checks each
+// tensor's size against the shapes the kernel is compiled for.
+struct StageParams {
+  const std::vector<torch::Tensor>& t;
+  size_t next = 0;
+  std::vector<const void*> ptrs;
+
+  explicit StageParams(const std::vector<torch::Tensor>& params) : t(params) {}
+
+  const torch::Tensor& take() {
+    TORCH_CHECK(next < t.size(), "too few stage parameters");
+    return t[next++];
+  }
+  // packed conv weight [cout/16][ceil(k/32)][64][8] bf16, then fp32 bias
+  void conv(int64_t k, int64_t cout) {
+    const torch::Tensor& w = take();
+    TORCH_CHECK(w.numel() == (cout / 16) * ((k + 31) / 32) * 512,
+                "packed conv weight has the wrong size");
+    ptrs.push_back(bf16_ptr(w));
+    f32(cout);
+  }
+  void f32(int64_t n) {
+    const torch::Tensor& b = take();
+    TORCH_CHECK(b.is_cuda() && b.dtype() == torch::kFloat32 &&
+                    b.is_contiguous() && b.numel() == n,
+                "fp32 stage parameter has the wrong type or size");
+    ptrs.push_back(b.data_ptr<float>());
+  }
+  void res(int64_t c) {
+    conv(9 * c, c);
+    conv(9 * c, c);
+  }
+  void down(int64_t c) {
+    conv(9 * c, 2 * c);
+    conv(18 * c, 2 * c);
+    conv(c, 2 * c);
+  }
+  const void* const* done() {
+    TORCH_CHECK(next == t.size(), "too many stage parameters");
+    return ptrs.data();
+  }
+};
+
+void check_plane(const torch::Tensor& x, int64_t elems) {
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == elems, "x must be [B, ", elems, "]");
+}
+
+// x: fp32 [B, 32, 32, 3] contiguous. params: stem w, b; 3 x (w1, b1, w2, b2);
+// down w1, b1, w2, b2, wsc, bsc. Returns the stage-1 plane bf16 [B, 16*16*32].
+torch::Tensor resnet_stage1(torch::Tensor x,
+                            std::vector<torch::Tensor> params) {
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kFloat32 &&
+                  x.is_contiguous() && x.dim() == 4 && x.size(1) == 32 &&
+                  x.size(2) == 32 && x.size(3) == 3,
+              "x must be a contiguous fp32 [B, 32, 32, 3] GPU tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  StageParams p(params);
+  p.conv(9 * 8, 16);
+  for (int i = 0; i < 3; ++i) p.res(16);
+  p.down(16);
+  const void* const* ptrs = p.done();
+  const int batch = x.size(0);
+  auto out = torch::empty({batch, 16 * 16 * 32},
+                          x.options().dtype(torch::kBFloat16));
+  if (batch > 0)
+    launch_stage1(batch, x.data_ptr<float>(),
+                  const_cast<short*>(bf16_ptr(out)), ptrs, cur_stream());
+  return out;
+}
+
+// x: bf16 [B, 16*16*32]. params: 2 x (w1, b1, w2, b2); down (6).
+// Returns the stage-2 plane bf16 [B, 8*8*64].
+torch::Tensor resnet_stage2(torch::Tensor x,
+                            std::vector<torch::Tensor> params) {
+  check_plane(x, 16 * 16 * 32);
+  StageParams p(params);
+  for (int i = 0; i < 2; ++i) p.res(32);
+  p.down(32);
+  const void* const* ptrs = p.done();
+  const int batch = x.size(0);
+  auto out = torch::empty({batch, 8 * 8 * 64}, x.options());
+  if (batch > 0)
+    launch_stage2(batch, bf16_ptr(x), const_cast<short*>(bf16_ptr(out)), ptrs,
+                  cur_stream());
+  return out;
+}
+
+// x: bf16 [B, 8*8*64]. params: 2 x (w1, b1, w2, b2); fc w [10, 64], b [10].
+// Returns (stage-3 ATs bf16 [B, 4096], logits fp32 [B, 10]).
+std::vector<torch::Tensor> resnet_stage3(torch::Tensor x,
+                                         std::vector<torch::Tensor> params) {
+  check_plane(x, 8 * 8 * 64);
+  StageParams p(params);
+  for (int i = 0; i < 2; ++i) p.res(64);
+  p.f32(10 * 64);
+  p.f32(10);
+  const void* const* ptrs = p.done();
+  const int batch = x.size(0);
+  auto ats = torch::empty_like(x);
+  auto logits = torch::empty({batch, 10}, x.options().dtype(torch::kFloat32));
+  if (batch > 0)
+    launch_stage3(batch, bf16_ptr(x), const_cast<short*>(bf16_ptr(ats)),
+                  logits.data_ptr<float>(), ptrs, cur_stream());
+  return {ats, logits};
+}
+
 // ---- fused MC-dropout head (variation-ratio votes) ----
 
 // thresh = floor(p * 2^32) and scale = float32(1 / (1 - p)) are computed once
@@ -778,6 +891,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resnet_block", &resnet_block);
   m.def("resnet_down", &resnet_down);
   m.def("resnet_stem", &resnet_stem);
+  m.def("resnet_stage1", &resnet_stage1);
+  m.def("resnet_stage2", &resnet_stage2);
+  m.def("resnet_stage3", &resnet_stage3);
   m.def("mc_dropout_votes", &mc_dropout_votes);
   m.def("mc_dropout_stats", &mc_dropout_stats);
   m.def("mc_dropout_max_grid", &mc_dropout_max_grid);
