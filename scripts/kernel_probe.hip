@@ -243,9 +243,9 @@ static void run_grouped(int iters, int perclass_test, int perclass_train,
     dsum += dh[i];
     isum += ih[i];
   }
-  printf("grouped_rowmin C=%d bp=%d ntr/cls=%d k=%d (GXY=%d): %.3f ms/iter, "
+  printf("grouped_rowmin C=%d bp=%d ntr/cls=%d k=%d: %.3f ms/iter, "
          "%.1f TF  checksum d=%.6e i=%lld\n",
-         C, bp, perclass_train, k, TIP_GXY, ms / iters, tf, dsum, isum);
+         C, bp, perclass_train, k, ms / iters, tf, dsum, isum);
 }
 
 // Determinism + correctness check: launch the grouped rowmin twice into

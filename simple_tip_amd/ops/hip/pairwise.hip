@@ -1,4 +1,4 @@
-// MFMA fp32 pairwise-distance kernel family for gfx950 (CDNA4).
+// MFMA pairwise-distance kernel family for gfx950 (CDNA4).
 //
 // The workload's hot core: squared L2 distances
 // between a test-AT matrix A [M,K] and a train-AT matrix B [N,K], computed
@@ -13,6 +13,25 @@
 //
 // Geometry: 256 threads = 4 waves as 2x2; block tile 128x128, K-step 32;
 // each wave owns a 64x64 sub-tile = 2x2 MFMA 32x32 accumulators.
+//
+// Structure. A kernel is index computation around shared device code, each
+// piece of which exists once:
+//   tile_mainloop_f32    fp32 staging + MFMA loop of one 128x128 tile
+//   tile_epilogue_f32    fp32 per-row epilogue (distance, clamp, half-wave
+//                        reduction into red_*), then merge_halves_store
+//   merge_halves_store   merges the two 64-column halves of a block row
+//                        (kde_merge_pair for KDE) and writes the partial;
+//                        the fp32 kernels and the bf16 kernel all end in it
+//   fold_rowmin/fold_kde fold the column-block partials of one row, bj
+//                        ascending; all six combine kernels call them
+//   class_of_row         class of a padded row from the segment table
+// pairwise_kernel (flat: XCD swizzle, EPI_FULL) and grouped_pairwise_kernel
+// (class segments) differ only in how a block finds its tile and its bounds,
+// so a grouped result equals the per-class flat result bit for bit, and the
+// plan-driven *_final_kernels fold exactly as the *_combine_kernels do.
+// grouped_pairwise_bf16_kernel keeps a main loop and per-row epilogue of its
+// own (16x16x32 bf16 MFMA, another fragment layout). Where one variant
+// behaves differently from its siblings, a comment at that line says so.
 
 #include "tip_common.h"
 
@@ -79,53 +98,26 @@ TIP_DEV void stage_write(float* lds, const StageRegs& sr) {
   }
 }
 
-template <int EPI>
-__launch_bounds__(256, 2) __global__ void pairwise_kernel(
-    const float* __restrict__ A,      // [M, K]
-    const float* __restrict__ B,      // [N, K]
-    const float* __restrict__ anorm,  // [M] row squared norms
-    const float* __restrict__ bnorm,  // [N]
-    int M, int N, int K,
-    float* __restrict__ out_full,     // EPI_FULL: [M, N]
-    float* __restrict__ pmin_val,     // EPI_ROWMIN: [jblocks, M]
-    int* __restrict__ pmin_idx,       //             [jblocks, M]
-    float2* __restrict__ pkde) {      // EPI_KDE:   [jblocks, M] (max, sum)
-  __shared__ float lds[2 * BK * (BM + LDS_PAD)];
-  float* As = lds;
-  float* Bs = lds + BK * (BM + LDS_PAD);
-  // reduction scratch: per block row x 2 column-halves
-  __shared__ float red_v[BM][2];
-  __shared__ int red_i[BM][2];
-  __shared__ float red_s[BM][2];
+// The wave's 64x64 sub-tile of A.B^T: t[m][n] is the 32x32 accumulator of
+// row half m, column half n.
+struct TileAcc {
+  f32x16 t[2][2];
+};
 
-  // XCD-aware block swizzle (T1, bijective form): consecutive remapped ids
-  // land on one XCD and share the A panel in that XCD's L2.
-  const int jblocks = gridDim.x;
-  int bi, bj;
-  {
-    const int nwg = gridDim.x * gridDim.y;
-    const int id = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q = nwg / 8, r = nwg % 8;
-    const int xcd = id % 8, pos = id / 8;
-    const int newid =
-        (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    bi = newid / gridDim.x;
-    bj = newid % gridDim.x;
-  }
-  const int row0 = bi * BM;
-  const int col0 = bj * BN;
-
+// fp32 main loop of the block tile at (row0, col0). T14 pipeline: the
+// prologue stages tile 0; each iteration issues tile t+1's global loads
+// before tile t's MFMAs and writes them to LDS afterwards. Rows of A at or
+// past a_rows and rows of B at or past b_rows stage zeros.
+TIP_DEV TileAcc tile_mainloop_f32(
+    const float* __restrict__ A, int a_rows, const float* __restrict__ B,
+    int b_rows, int K, int row0, int col0, float* As, float* Bs) {
   const int lane = lane_id();
-  const int wid = wave_id();
-  const int wr = wid >> 1;  // wave row (0..1) -> 64 rows
-  const int wc = wid & 1;   // wave col (0..1) -> 64 cols
+  const int wr = wave_id() >> 1;  // wave row (0..1) -> 64 rows
+  const int wc = wave_id() & 1;   // wave col (0..1) -> 64 cols
 
-  f32x16 acc[2][2] = {};
-
-  // T14 pipeline: prologue stages tile 0; each iteration issues tile t+1's
-  // global loads before tile t's MFMAs and writes them to LDS afterwards.
-  StageRegs ra = stage_load(A, M, K, row0, 0);
-  StageRegs rb = stage_load(B, N, K, col0, 0);
+  TileAcc acc = {};
+  StageRegs ra = stage_load(A, a_rows, K, row0, 0);
+  StageRegs rb = stage_load(B, b_rows, K, col0, 0);
   stage_write(As, ra);
   stage_write(Bs, rb);
   __syncthreads();
@@ -133,8 +125,8 @@ __launch_bounds__(256, 2) __global__ void pairwise_kernel(
   for (int k0 = 0; k0 < K; k0 += BK) {
     const bool has_next = (k0 + BK) < K;
     if (has_next) {
-      ra = stage_load(A, M, K, row0, k0 + BK);
-      rb = stage_load(B, N, K, col0, k0 + BK);
+      ra = stage_load(A, a_rows, K, row0, k0 + BK);
+      rb = stage_load(B, b_rows, K, col0, k0 + BK);
     }
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 2) {
@@ -143,10 +135,10 @@ __launch_bounds__(256, 2) __global__ void pairwise_kernel(
       const float* bs = &Bs[k * (BM + LDS_PAD) + wc * 64 + (lane & 31)];
       const float a0 = as[0], a1 = as[32];
       const float b0 = bs[0], b1 = bs[32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+      acc.t[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc.t[0][0], 0, 0, 0);
+      acc.t[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc.t[0][1], 0, 0, 0);
+      acc.t[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc.t[1][0], 0, 0, 0);
+      acc.t[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc.t[1][1], 0, 0, 0);
     }
     __syncthreads();  // all reads of tile t done
     if (has_next) {
@@ -155,13 +147,63 @@ __launch_bounds__(256, 2) __global__ void pairwise_kernel(
     }
     __syncthreads();  // tile t+1 visible
   }
+  return acc;
+}
 
-  // ---- epilogue ----
-  // C/D layout of v_mfma_f32_32x32x2_f32 (standard 32x32 map):
-  //   col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+// Streaming-logsumexp merge of two (max, sum) pairs; a pair with sum 0 is
+// empty and its max is not looked at.
+TIP_DEV float2 kde_merge_pair(float m0, float s0, float m1, float s1) {
+  if (m0 >= m1)
+    return make_float2(m0, s0 + ((s1 > 0.f) ? s1 * __expf(m1 - m0) : 0.f));
+  return make_float2(m1, s1 + ((s0 > 0.f) ? s0 * __expf(m0 - m1) : 0.f));
+}
+
+// Merge the two 64-column halves of every block row (red_*[r][wc]; wc = 0
+// covers the lower columns, so ties prefer it) and store the block's partial
+// for column block bj. Rows at or past row_end store nothing. The caller has
+// put a barrier between the writes to red_* and this call.
+template <int EPI>
+TIP_DEV void merge_halves_store(
+    const float (*red_v)[2], const int (*red_i)[2], const float (*red_s)[2],
+    int row0, int row_end, int stride, int bj, float* __restrict__ pmin_val,
+    int* __restrict__ pmin_idx, float2* __restrict__ pkde) {
+  for (int r = threadIdx.x; r < BM; r += blockDim.x) {
+    const int i = row0 + r;
+    if (i >= row_end) continue;
+    if (EPI == EPI_ROWMIN) {
+      const MinIdx best = min_idx_combine(
+          MinIdx{red_v[r][0], red_i[r][0]}, MinIdx{red_v[r][1], red_i[r][1]});
+      pmin_val[(int64_t)bj * stride + i] = best.v;
+      pmin_idx[(int64_t)bj * stride + i] = best.i;
+    } else {
+      pkde[(int64_t)bj * stride + i] =
+          kde_merge_pair(red_v[r][0], red_s[r][0], red_v[r][1], red_s[r][1]);
+    }
+  }
+}
+
+// fp32 epilogue of the block tile at (row0, col0): distances of rows below
+// row_end against columns below col_end, then the EPI's output. EPI_FULL
+// writes the [row_end, col_end] matrix out_full; the others write the
+// partial of column block bj, [*, stride].
+// C/D layout of v_mfma_f32_32x32x2_f32 (standard 32x32 map):
+//   col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+template <int EPI>
+TIP_DEV void tile_epilogue_f32(
+    const TileAcc& acc, const float* __restrict__ anorm,
+    const float* __restrict__ bnorm, int row0, int row_end, int col0,
+    int col_end, int stride, int bj, float (*red_v)[2], int (*red_i)[2],
+    float (*red_s)[2], float* __restrict__ out_full,
+    float* __restrict__ pmin_val, int* __restrict__ pmin_idx,
+    float2* __restrict__ pkde) {
+  const int lane = lane_id();
+  const int wr = wave_id() >> 1;
+  const int wc = wave_id() & 1;
   const int jl0 = col0 + wc * 64 + (lane & 31);  // n=0 column
-  const float bn0 = (jl0 < N) ? bnorm[jl0] : 0.f;
-  const float bn1 = (jl0 + 32 < N) ? bnorm[jl0 + 32] : 0.f;
+  // differs from the bf16 epilogue, which reads bnorm per tile column
+  // inside the range guard
+  const float bn0 = (jl0 < col_end) ? bnorm[jl0] : 0.f;
+  const float bn1 = (jl0 + 32 < col_end) ? bnorm[jl0 + 32] : 0.f;
 
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
@@ -171,18 +213,19 @@ __launch_bounds__(256, 2) __global__ void pairwise_kernel(
       const int row_local = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
       const int block_row = wr * 64 + m * 32 + row_local;
       const int i = row0 + block_row;
-      const float an = (i < M) ? anorm[i] : 0.f;
-      float d0 = an + bn0 - 2.f * acc[m][0][reg];
-      float d1 = an + bn1 - 2.f * acc[m][1][reg];
+      const float an = (i < row_end) ? anorm[i] : 0.f;
+      float d0 = an + bn0 - 2.f * acc.t[m][0][reg];
+      float d1 = an + bn1 - 2.f * acc.t[m][1][reg];
       d0 = fmaxf(d0, 0.f);
       d1 = fmaxf(d1, 0.f);
-      if (jl0 >= N) d0 = FLT_MAX;
-      if (jl0 + 32 >= N) d1 = FLT_MAX;
+      if (jl0 >= col_end) d0 = FLT_MAX;
+      if (jl0 + 32 >= col_end) d1 = FLT_MAX;
 
       if (EPI == EPI_FULL) {
-        if (i < M) {
-          if (jl0 < N) out_full[(int64_t)i * N + jl0] = d0;
-          if (jl0 + 32 < N) out_full[(int64_t)i * N + jl0 + 32] = d1;
+        if (i < row_end) {
+          if (jl0 < col_end) out_full[(int64_t)i * col_end + jl0] = d0;
+          if (jl0 + 32 < col_end)
+            out_full[(int64_t)i * col_end + jl0 + 32] = d1;
         }
       } else if (EPI == EPI_ROWMIN) {
         MinIdx mi{d0, jl0};
@@ -196,7 +239,9 @@ __launch_bounds__(256, 2) __global__ void pairwise_kernel(
         MinIdx mi{d0, 0};
         mi = min_idx_combine(mi, MinIdx{d1, 0});
         mi = half_reduce_min(mi);
-        const float tmax = -0.5f * mi.v;  // = max_j(-d/2) over these 64 cols
+        // = max_j(-d/2) over these 64 cols. Differs from the bf16 epilogue:
+        // a half with no column in range gives -0.5f * FLT_MAX here
+        const float tmax = -0.5f * mi.v;
         float s = 0.f;
         if (d0 != FLT_MAX) s += __expf(-0.5f * d0 - tmax);
         if (d1 != FLT_MAX) s += __expf(-0.5f * d1 - tmax);
@@ -211,41 +256,67 @@ __launch_bounds__(256, 2) __global__ void pairwise_kernel(
 
   if (EPI == EPI_FULL) return;
   __syncthreads();
-  // combine the two column-halves (wc=0 covers lower j: ties prefer it)
-  for (int r = threadIdx.x; r < BM; r += blockDim.x) {
-    const int i = row0 + r;
-    if (i >= M) continue;
-    if (EPI == EPI_ROWMIN) {
-      MinIdx a{red_v[r][0], red_i[r][0]};
-      MinIdx b{red_v[r][1], red_i[r][1]};
-      MinIdx best = min_idx_combine(a, b);
-      pmin_val[(int64_t)bj * M + i] = best.v;
-      pmin_idx[(int64_t)bj * M + i] = best.i;
-    } else if (EPI == EPI_KDE) {
-      float m0 = red_v[r][0], s0 = red_s[r][0];
-      float m1 = red_v[r][1], s1 = red_s[r][1];
-      float mm, ss;
-      if (m0 >= m1) {
-        mm = m0;
-        ss = s0 + ((s1 > 0.f) ? s1 * __expf(m1 - m0) : 0.f);
-      } else {
-        mm = m1;
-        ss = s1 + ((s0 > 0.f) ? s0 * __expf(m0 - m1) : 0.f);
-      }
-      pkde[(int64_t)bj * M + i] = make_float2(mm, ss);
-    }
+  merge_halves_store<EPI>(red_v, red_i, red_s, row0, row_end, stride, bj,
+                          pmin_val, pmin_idx, pkde);
+}
+
+// Class of padded row `row`: the last class whose segment starts at or
+// before it (segments are 128-aligned, so one row block is one class).
+TIP_DEV int class_of_row(const int* __restrict__ tseg, int nclasses, int row) {
+  int cls = 0;
+  for (int c = 0; c < nclasses; ++c)
+    if (tseg[c] <= row) cls = c;
+  return cls;
+}
+
+template <int EPI>
+__launch_bounds__(256, 2) __global__ void pairwise_kernel(
+    const float* __restrict__ A,      // [M, K]
+    const float* __restrict__ B,      // [N, K]
+    const float* __restrict__ anorm,  // [M] row squared norms
+    const float* __restrict__ bnorm,  // [N]
+    int M, int N, int K,
+    float* __restrict__ out_full,     // EPI_FULL: [M, N]
+    float* __restrict__ pmin_val,     // EPI_ROWMIN: [jblocks, M]
+    int* __restrict__ pmin_idx,       //             [jblocks, M]
+    float2* __restrict__ pkde) {      // EPI_KDE:   [jblocks, M] (max, sum)
+  __shared__ float lds[2 * BK * (BM + LDS_PAD)];
+  // reduction scratch: per block row x 2 column-halves
+  __shared__ float red_v[BM][2];
+  __shared__ int red_i[BM][2];
+  __shared__ float red_s[BM][2];
+
+  // XCD-aware block swizzle (T1, bijective form): consecutive remapped ids
+  // land on one XCD and share the A panel in that XCD's L2.
+  int bi, bj;
+  {
+    const int nwg = gridDim.x * gridDim.y;
+    const int id = blockIdx.y * gridDim.x + blockIdx.x;
+    const int q = nwg / 8, r = nwg % 8;
+    const int xcd = id % 8, pos = id / 8;
+    const int newid =
+        (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+    bi = newid / gridDim.x;
+    bj = newid % gridDim.x;
   }
+  const int row0 = bi * BM;
+  const int col0 = bj * BN;
+
+  const TileAcc acc = tile_mainloop_f32(A, M, B, N, K, row0, col0, lds,
+                                        lds + BK * (BM + LDS_PAD));
+  tile_epilogue_f32<EPI>(acc, anorm, bnorm, row0, M, col0, N, M, bj, red_v,
+                         red_i, red_s, out_full, pmin_val, pmin_idx, pkde);
 }
 
 // ---------------------------------------------------------------------------
 // Grouped (segmented) variant: test rows are sorted by class and padded to
 // 128-row segments (tseg offsets, C+1 entries); train rows are the
 // class-concatenated set with raw offsets (nseg). One launch covers every
-// class — the per-class python loop (10+ launches, ~200 host ops per step)
-// becomes one kernel + one combine. Each block derives its class from its
-// row-block (segments are 128-aligned), and only columns inside the class's
-// train range participate. Argmin indices are GLOBAL train rows, so the
-// precomputed DSA b-table gathers directly.
+// class. Each block derives its class from its row-block (segments are
+// 128-aligned), and only columns inside the class's train range
+// participate. Argmin indices are GLOBAL train rows, so the precomputed DSA
+// b-table gathers directly. Column block fast, row block slow: the mapping
+// kept from the sweep in profiles/r02_grouped_mapping_sweep.md.
 // ---------------------------------------------------------------------------
 
 template <int EPI>
@@ -256,278 +327,28 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_kernel(
     const float* __restrict__ bnorm,  // [Ntot]
     const int* __restrict__ tseg,     // [C+1] padded test offsets (x128)
     const int* __restrict__ nseg,     // [C+1] train offsets
-    int nclasses, int Bp, int K, int jb_max_g,
+    int nclasses, int Bp, int K,
     float* __restrict__ pmin_val,     // [jb_max, Bp]
     int* __restrict__ pmin_idx,
     float2* __restrict__ pkde) {
   __shared__ float lds[2 * BK * (BM + LDS_PAD)];
-  float* As = lds;
-  float* Bs = lds + BK * (BM + LDS_PAD);
   __shared__ float red_v[BM][2];
   __shared__ int red_i[BM][2];
   __shared__ float red_s[BM][2];
 
-  // Block->tile mapping. TIP_GXY selects the variant (hardware-swept):
-  //  0: bi = blockIdx.y, bj = blockIdx.x (column block fast — baseline)
-  //  1: grid swapped, row block fast: consecutive ids share a column tile
-  //  2: XCD-aware (1-D grid padded to 8*per): consecutive block ids land on
-  //     different XCDs (round-robin dispatch), so give each XCD a
-  //     CONTIGUOUS tile range decomposed row-block-fast — every XCD sweeps
-  //     the row blocks of one (or few) column tiles and its 2-MB B tile
-  //     stays L2-resident while the A tiles stream.
-#ifndef TIP_GXY
-#define TIP_GXY 0
-#endif
-  int bi, bj;
-#if TIP_GXY == 0
-  bi = blockIdx.y;
-  bj = blockIdx.x;
-#elif TIP_GXY == 1
-  bi = blockIdx.x;
-  bj = blockIdx.y;
-#else
-  {
-    // 1-D grid of 8*per blocks (per = ceil(nrows*jb_max/8))
-    const int nrows = (Bp + BM - 1) / BM;
-    const int total = nrows * jb_max_g;
-    constexpr int NXCD = 8;
-    const int per = gridDim.x / NXCD;
-    const int t0 = blockIdx.x;
-    const int t = (t0 % NXCD) * per + t0 / NXCD;
-    if (t >= total) return;
-    bi = t % nrows;
-    bj = t / nrows;
-  }
-#endif
-  const int row0 = bi * BM;
+  const int bj = blockIdx.x;
+  const int row0 = blockIdx.y * BM;
   if (row0 >= Bp) return;
-  // class of this 128-aligned row block
-  int cls = 0;
-  for (int c = 0; c < nclasses; ++c)
-    if (tseg[c] <= row0) cls = c;
-  const int ncol0 = nseg[cls], ncol1 = nseg[cls + 1];
-  const int col0 = ncol0 + bj * BN;
+  const int cls = class_of_row(tseg, nclasses, row0);
+  const int ncol1 = nseg[cls + 1];
+  const int col0 = nseg[cls] + bj * BN;
   if (col0 >= ncol1) return;  // this class has fewer column blocks
 
-  const int lane = lane_id();
-  const int wid = wave_id();
-  const int wr = wid >> 1;
-  const int wc = wid & 1;
-
-  f32x16 acc[2][2] = {};
-  StageRegs ra = stage_load(A, Bp, K, row0, 0);
-  StageRegs rb = stage_load(B, ncol1, K, col0, 0);
-  stage_write(As, ra);
-  stage_write(Bs, rb);
-  __syncthreads();
-  for (int k0 = 0; k0 < K; k0 += BK) {
-    const bool has_next = (k0 + BK) < K;
-    if (has_next) {
-      ra = stage_load(A, Bp, K, row0, k0 + BK);
-      rb = stage_load(B, ncol1, K, col0, k0 + BK);
-    }
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 2) {
-      const int k = kk + (lane >> 5);
-      const float* as = &As[k * (BM + LDS_PAD) + wr * 64 + (lane & 31)];
-      const float* bs = &Bs[k * (BM + LDS_PAD) + wc * 64 + (lane & 31)];
-      const float a0 = as[0], a1 = as[32];
-      const float b0 = bs[0], b1 = bs[32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    __syncthreads();
-    if (has_next) {
-      stage_write(As, ra);
-      stage_write(Bs, rb);
-    }
-    __syncthreads();
-  }
-
-  const int jl0 = col0 + wc * 64 + (lane & 31);
-  const float bn0 = (jl0 < ncol1) ? bnorm[jl0] : 0.f;
-  const float bn1 = (jl0 + 32 < ncol1) ? bnorm[jl0 + 32] : 0.f;
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int row_local = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-      const int block_row = wr * 64 + m * 32 + row_local;
-      const int i = row0 + block_row;
-      const float an = (i < Bp) ? anorm[i] : 0.f;
-      float d0 = fmaxf(an + bn0 - 2.f * acc[m][0][reg], 0.f);
-      float d1 = fmaxf(an + bn1 - 2.f * acc[m][1][reg], 0.f);
-      if (jl0 >= ncol1) d0 = FLT_MAX;
-      if (jl0 + 32 >= ncol1) d1 = FLT_MAX;
-      if (EPI == EPI_ROWMIN) {
-        MinIdx mi{d0, jl0};
-        mi = min_idx_combine(mi, MinIdx{d1, jl0 + 32});
-        mi = half_reduce_min(mi);
-        if ((lane & 31) == 0) {
-          red_v[block_row][wc] = mi.v;
-          red_i[block_row][wc] = mi.i;
-        }
-      } else {
-        MinIdx mi{d0, 0};
-        mi = min_idx_combine(mi, MinIdx{d1, 0});
-        mi = half_reduce_min(mi);
-        const float tmax = -0.5f * mi.v;
-        float s = 0.f;
-        if (d0 != FLT_MAX) s += __expf(-0.5f * d0 - tmax);
-        if (d1 != FLT_MAX) s += __expf(-0.5f * d1 - tmax);
-        s = half_reduce_sum(s);
-        if ((lane & 31) == 0) {
-          red_v[block_row][wc] = tmax;
-          red_s[block_row][wc] = s;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int r = threadIdx.x; r < BM; r += blockDim.x) {
-    const int i = row0 + r;
-    if (i >= Bp) continue;
-    if (EPI == EPI_ROWMIN) {
-      MinIdx best = min_idx_combine(
-          MinIdx{red_v[r][0], red_i[r][0]}, MinIdx{red_v[r][1], red_i[r][1]});
-      pmin_val[(int64_t)bj * Bp + i] = best.v;
-      pmin_idx[(int64_t)bj * Bp + i] = best.i;
-    } else {
-      float m0 = red_v[r][0], s0 = red_s[r][0];
-      float m1 = red_v[r][1], s1 = red_s[r][1];
-      float mm, ss;
-      if (m0 >= m1) {
-        mm = m0;
-        ss = s0 + ((s1 > 0.f) ? s1 * __expf(m1 - m0) : 0.f);
-      } else {
-        mm = m1;
-        ss = s1 + ((s0 > 0.f) ? s0 * __expf(m0 - m1) : 0.f);
-      }
-      pkde[(int64_t)bj * Bp + i] = make_float2(mm, ss);
-    }
-  }
-}
-
-__global__ void grouped_rowmin_combine_kernel(
-    const float* __restrict__ pval, const int* __restrict__ pidx,
-    const int* __restrict__ tseg, const int* __restrict__ nseg, int nclasses,
-    int Bp, float* __restrict__ out_dist, int64_t* __restrict__ out_idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Bp) return;
-  int cls = 0;
-  for (int c = 0; c < nclasses; ++c)
-    if (tseg[c] <= i) cls = c;
-  const int jcount = (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
-  MinIdx best{FLT_MAX, 0x7fffffff};
-  for (int b = 0; b < jcount; ++b)
-    best = min_idx_combine(
-        best, MinIdx{pval[(int64_t)b * Bp + i], pidx[(int64_t)b * Bp + i]});
-  if (jcount == 0) {
-    out_dist[i] = FLT_MAX;
-    out_idx[i] = -1;
-  } else {
-    out_dist[i] = sqrtf(best.v);
-    out_idx[i] = best.i;
-  }
-}
-
-__global__ void grouped_kde_combine_kernel(
-    const float2* __restrict__ pkde, const int* __restrict__ tseg,
-    const int* __restrict__ nseg, int nclasses, int Bp,
-    float* __restrict__ out_lse) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Bp) return;
-  int cls = 0;
-  for (int c = 0; c < nclasses; ++c)
-    if (tseg[c] <= i) cls = c;
-  const int jcount = (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
-  float mm = -FLT_MAX, ss = 0.f;
-  for (int b = 0; b < jcount; ++b) {
-    const float2 p = pkde[(int64_t)b * Bp + i];
-    if (p.y <= 0.f) continue;
-    if (p.x > mm) {
-      ss = p.y + ((ss > 0.f) ? ss * __expf(mm - p.x) : 0.f);
-      mm = p.x;
-    } else {
-      ss += p.y * __expf(p.x - mm);
-    }
-  }
-  out_lse[i] = (ss > 0.f) ? (mm + __logf(ss)) : -FLT_MAX;
-}
-
-// Plan-driven combines (sync-free scoring path): the same fixed-order folds,
-// but each padded row p writes its FINAL score to its source row rowmap[p].
-// Pad rows and rows at or past tseg[nclasses] write nothing, so the outputs
-// (pre-filled with +inf by the caller) never see stale workspace content.
-__global__ void grouped_rowmin_final_kernel(
-    const float* __restrict__ pval, const int* __restrict__ pidx,
-    const int* __restrict__ tseg, const int* __restrict__ nseg, int nclasses,
-    int Bp, const int* __restrict__ rowmap, int out_rows,
-    const float* __restrict__ btable, float* __restrict__ out_dsa,
-    float* __restrict__ out_dist, int* __restrict__ out_idx) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Bp || i >= tseg[nclasses]) return;
-  const int src = rowmap[i];
-  if (src < 0 || src >= out_rows) return;
-  int cls = 0;
-  for (int c = 0; c < nclasses; ++c)
-    if (tseg[c] <= i) cls = c;
-  const int jcount = (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
-  MinIdx best{FLT_MAX, 0x7fffffff};
-  for (int b = 0; b < jcount; ++b)
-    best = min_idx_combine(
-        best, MinIdx{pval[(int64_t)b * Bp + i], pidx[(int64_t)b * Bp + i]});
-  if (jcount == 0) {
-    out_dsa[src] = INFINITY;
-    out_dist[src] = FLT_MAX;
-    out_idx[src] = -1;
-  } else if ((unsigned)best.i >= (unsigned)nseg[nclasses]) {
-    // every distance was NaN (non-finite activations): no argmin to gather
-    out_dsa[src] = NAN;
-    out_dist[src] = NAN;
-    out_idx[src] = -1;
-  } else {
-    const float dist = sqrtf(best.v);
-    out_dsa[src] = dist / btable[best.i];
-    out_dist[src] = dist;
-    out_idx[src] = best.i;
-  }
-}
-
-__global__ void grouped_kde_final_kernel(
-    const float2* __restrict__ pkde, const int* __restrict__ tseg,
-    const int* __restrict__ nseg, int nclasses, int Bp,
-    const int* __restrict__ rowmap, int out_rows,
-    const int* __restrict__ cls_fused,    // [C] 1: KDE class, 0: constant
-    const float* __restrict__ cls_const,  // [C] KDE constant / the score
-    float* __restrict__ out_lsa) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Bp || i >= tseg[nclasses]) return;
-  const int src = rowmap[i];
-  if (src < 0 || src >= out_rows) return;
-  int cls = 0;
-  for (int c = 0; c < nclasses; ++c)
-    if (tseg[c] <= i) cls = c;
-  if (!cls_fused[cls]) {
-    out_lsa[src] = cls_const[cls];
-    return;
-  }
-  const int jcount = (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
-  float mm = -FLT_MAX, ss = 0.f;
-  for (int b = 0; b < jcount; ++b) {
-    const float2 p = pkde[(int64_t)b * Bp + i];
-    if (p.y <= 0.f) continue;
-    if (p.x > mm) {
-      ss = p.y + ((ss > 0.f) ? ss * __expf(mm - p.x) : 0.f);
-      mm = p.x;
-    } else {
-      ss += p.y * __expf(p.x - mm);
-    }
-  }
-  const float lse = (ss > 0.f) ? (mm + __logf(ss)) : -FLT_MAX;
-  out_lsa[src] = -(lse + cls_const[cls]);
+  const TileAcc acc = tile_mainloop_f32(A, Bp, B, ncol1, K, row0, col0, lds,
+                                        lds + BK * (BM + LDS_PAD));
+  tile_epilogue_f32<EPI>(acc, anorm, bnorm, row0, Bp, col0, ncol1, Bp, bj,
+                         red_v, red_i, red_s, nullptr, pmin_val, pmin_idx,
+                         pkde);
 }
 
 // ---------------------------------------------------------------------------
@@ -623,11 +444,10 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
   const int bi = blockIdx.y;
   const int bj = blockIdx.x;
   const int row0 = bi * BM;
-  // a row block past the last segment belongs to no class
+  // a row block past the last segment belongs to no class (differs from the
+  // fp32 grouped kernel, whose row bound is Bp alone)
   if (row0 >= tseg[nclasses]) return;
-  int cls = 0;
-  for (int c = 0; c < nclasses; ++c)
-    if (tseg[c] <= row0) cls = c;
+  const int cls = class_of_row(tseg, nclasses, row0);
   const int ncol0 = nseg[cls], ncol1 = nseg[cls + 1];
   const int col0 = ncol0 + bj * BN;
   if (col0 >= ncol1) return;
@@ -703,6 +523,8 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
       for (int tc = 0; tc < 4; ++tc) {
         const int gj = col0 + wc * 64 + tc * 16 + fj;
         float d;
+        // differs from the fp32 epilogue, which preloads bn0 / bn1 and
+        // overwrites the out-of-range distances afterwards
         if (gj < ncol1) {
           d = fmaxf(an + bnorm[gj] - 2.f * acc[tr][tc][reg], 0.f);
         } else {
@@ -724,6 +546,8 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
           red_i[row_local][wc] = mi.i;
         }
       } else {
+        // differs from the fp32 epilogue, which takes -0.5f * min even for
+        // a half with no column in range
         const float tmax = (mi.v == FLT_MAX) ? -FLT_MAX : -0.5f * mi.v;
         float s = 0.f;
 #pragma unroll
@@ -738,42 +562,56 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
     }
   }
   __syncthreads();
-  for (int r = threadIdx.x; r < BM; r += blockDim.x) {
-    const int i = row0 + r;
-    if (i >= Bp) continue;
-    if (EPI == EPI_ROWMIN) {
-      MinIdx best = min_idx_combine(
-          MinIdx{red_v[r][0], red_i[r][0]}, MinIdx{red_v[r][1], red_i[r][1]});
-      pmin_val[(int64_t)bj * Bp + i] = best.v;
-      pmin_idx[(int64_t)bj * Bp + i] = best.i;
-    } else {
-      float m0 = red_v[r][0], s0 = red_s[r][0];
-      float m1 = red_v[r][1], s1 = red_s[r][1];
-      float mm, ss;
-      if (m0 >= m1) {
-        mm = m0;
-        ss = s0 + ((s1 > 0.f) ? s1 * __expf(m1 - m0) : 0.f);
-      } else {
-        mm = m1;
-        ss = s1 + ((s0 > 0.f) ? s0 * __expf(m0 - m1) : 0.f);
-      }
-      pkde[(int64_t)bj * Bp + i] = make_float2(mm, ss);
-    }
-  }
+  merge_halves_store<EPI>(red_v, red_i, red_s, row0, Bp, Bp, bj, pmin_val,
+                          pmin_idx, pkde);
 }
 
-// Deterministic cross-block-column combines (ascending bj keeps np.argmin
-// lowest-index tie semantics; fixed order keeps results bitwise stable).
+// ---------------------------------------------------------------------------
+// Cross-block-column combines. One thread per row folds that row's jcount
+// partials (row i of column block b is at [b * stride + i]) in ascending b:
+// ascending keeps np.argmin's lowest-index tie rule, a fixed order keeps the
+// results bitwise stable across launches and shard counts.
+// ---------------------------------------------------------------------------
+
+TIP_DEV MinIdx fold_rowmin(const float* __restrict__ pval,
+                           const int* __restrict__ pidx, int jcount,
+                           int stride, int i) {
+  MinIdx best{FLT_MAX, 0x7fffffff};
+  for (int b = 0; b < jcount; ++b)
+    best = min_idx_combine(best, MinIdx{pval[(int64_t)b * stride + i],
+                                        pidx[(int64_t)b * stride + i]});
+  return best;
+}
+
+// Streaming logsumexp over the (max, sum) partials; -FLT_MAX when every
+// partial is empty (jcount == 0, or every term underflowed).
+TIP_DEV float fold_kde(const float2* __restrict__ pkde, int jcount, int stride,
+                       int i) {
+  float mm = -FLT_MAX, ss = 0.f;
+  for (int b = 0; b < jcount; ++b) {
+    const float2 p = pkde[(int64_t)b * stride + i];
+    if (p.y <= 0.f) continue;
+    if (p.x > mm) {
+      ss = p.y + ((ss > 0.f) ? ss * __expf(mm - p.x) : 0.f);
+      mm = p.x;
+    } else {
+      ss += p.y * __expf(p.x - mm);
+    }
+  }
+  return (ss > 0.f) ? (mm + __logf(ss)) : -FLT_MAX;
+}
+
+// Column blocks of class cls.
+TIP_DEV int class_jcount(const int* __restrict__ nseg, int cls) {
+  return (nseg[cls + 1] - nseg[cls] + BN - 1) / BN;
+}
+
 __global__ void rowmin_combine_kernel(
     const float* __restrict__ pval, const int* __restrict__ pidx, int jblocks,
     int M, float* __restrict__ out_dist, int64_t* __restrict__ out_idx) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
-  MinIdx best{FLT_MAX, 0x7fffffff};
-  for (int b = 0; b < jblocks; ++b) {
-    MinIdx cand{pval[(int64_t)b * M + i], pidx[(int64_t)b * M + i]};
-    best = min_idx_combine(best, cand);
-  }
+  const MinIdx best = fold_rowmin(pval, pidx, jblocks, M, i);
   out_dist[i] = sqrtf(best.v);
   out_idx[i] = best.i;
 }
@@ -783,18 +621,92 @@ __global__ void kde_combine_kernel(
     float* __restrict__ out_lse) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
-  float mm = -FLT_MAX, ss = 0.f;
-  for (int b = 0; b < jblocks; ++b) {
-    const float2 p = pkde[(int64_t)b * M + i];
-    if (p.y <= 0.f) continue;
-    if (p.x > mm) {
-      ss = p.y + ((ss > 0.f) ? ss * __expf(mm - p.x) : 0.f);
-      mm = p.x;
-    } else {
-      ss += p.y * __expf(p.x - mm);
-    }
+  out_lse[i] = fold_kde(pkde, jblocks, M, i);
+}
+
+__global__ void grouped_rowmin_combine_kernel(
+    const float* __restrict__ pval, const int* __restrict__ pidx,
+    const int* __restrict__ tseg, const int* __restrict__ nseg, int nclasses,
+    int Bp, float* __restrict__ out_dist, int64_t* __restrict__ out_idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp) return;
+  const int jcount = class_jcount(nseg, class_of_row(tseg, nclasses, i));
+  const MinIdx best = fold_rowmin(pval, pidx, jcount, Bp, i);
+  if (jcount == 0) {
+    // differs from grouped_rowmin_final_kernel: FLT_MAX, and no NaN guard
+    out_dist[i] = FLT_MAX;
+    out_idx[i] = -1;
+  } else {
+    out_dist[i] = sqrtf(best.v);
+    out_idx[i] = best.i;
   }
-  out_lse[i] = (ss > 0.f) ? (mm + __logf(ss)) : -FLT_MAX;
+}
+
+__global__ void grouped_kde_combine_kernel(
+    const float2* __restrict__ pkde, const int* __restrict__ tseg,
+    const int* __restrict__ nseg, int nclasses, int Bp,
+    float* __restrict__ out_lse) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp) return;
+  const int jcount = class_jcount(nseg, class_of_row(tseg, nclasses, i));
+  out_lse[i] = fold_kde(pkde, jcount, Bp, i);
+}
+
+// Plan-driven combines (sync-free scoring path): the same folds, but each
+// padded row p writes its FINAL score to its source row rowmap[p]. Pad rows
+// and rows at or past tseg[nclasses] write nothing, so the outputs
+// (pre-filled with +inf by the caller) never see stale workspace content.
+__global__ void grouped_rowmin_final_kernel(
+    const float* __restrict__ pval, const int* __restrict__ pidx,
+    const int* __restrict__ tseg, const int* __restrict__ nseg, int nclasses,
+    int Bp, const int* __restrict__ rowmap, int out_rows,
+    const float* __restrict__ btable, float* __restrict__ out_dsa,
+    float* __restrict__ out_dist, int* __restrict__ out_idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp || i >= tseg[nclasses]) return;
+  const int src = rowmap[i];
+  if (src < 0 || src >= out_rows) return;
+  const int jcount = class_jcount(nseg, class_of_row(tseg, nclasses, i));
+  const MinIdx best = fold_rowmin(pval, pidx, jcount, Bp, i);
+  if (jcount == 0) {
+    // differs from grouped_rowmin_combine_kernel: the score is +inf
+    out_dsa[src] = INFINITY;
+    out_dist[src] = FLT_MAX;
+    out_idx[src] = -1;
+  } else if ((unsigned)best.i >= (unsigned)nseg[nclasses]) {
+    // every distance was NaN (non-finite activations): no argmin to gather.
+    // Only this kernel has the guard; the other two rowmin combines store
+    // the fold's initial index.
+    out_dsa[src] = NAN;
+    out_dist[src] = NAN;
+    out_idx[src] = -1;
+  } else {
+    const float dist = sqrtf(best.v);
+    out_dsa[src] = dist / btable[best.i];
+    out_dist[src] = dist;
+    out_idx[src] = best.i;
+  }
+}
+
+__global__ void grouped_kde_final_kernel(
+    const float2* __restrict__ pkde, const int* __restrict__ tseg,
+    const int* __restrict__ nseg, int nclasses, int Bp,
+    const int* __restrict__ rowmap, int out_rows,
+    const int* __restrict__ cls_fused,    // [C] 1: KDE class, 0: constant
+    const float* __restrict__ cls_const,  // [C] KDE constant / the score
+    float* __restrict__ out_lsa) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp || i >= tseg[nclasses]) return;
+  const int src = rowmap[i];
+  if (src < 0 || src >= out_rows) return;
+  const int cls = class_of_row(tseg, nclasses, i);
+  if (!cls_fused[cls]) {
+    out_lsa[src] = cls_const[cls];
+    return;
+  }
+  // differs from grouped_kde_combine_kernel: the negated, shifted score
+  const float lse = fold_kde(pkde, class_jcount(nseg, cls), Bp, i);
+  out_lsa[src] = -(lse + cls_const[cls]);
 }
 
 // Row squared norms: one wave per row.
@@ -849,25 +761,14 @@ void launch_pairwise_kde(const float* a, const float* b, const float* an,
   kde_combine_kernel<<<ceil_div(m, 256), 256, 0, s>>>(pkde, jb, m, out_lse);
 }
 
-// Grid geometry matching the kernel's TIP_GXY block->tile mapping.
-static dim3 grouped_grid(int bp, int jb_max) {
-#if TIP_GXY == 0
-  return dim3(jb_max, ceil_div(bp, BM));
-#elif TIP_GXY == 1
-  return dim3(ceil_div(bp, BM), jb_max);
-#else
-  const int total = ceil_div(bp, BM) * jb_max;
-  return dim3(8 * ceil_div(total, 8), 1);
-#endif
-}
-
 void launch_grouped_rowmin(const float* a, const float* b, const float* an,
                            const float* bn, const int* tseg, const int* nseg,
                            int nclasses, int bp, int k, int jb_max,
                            float* pval, int* pidx, float* out_dist,
                            int64_t* out_idx, hipStream_t s) {
-  grouped_pairwise_kernel<EPI_ROWMIN><<<grouped_grid(bp, jb_max), 256, 0, s>>>(
-      a, b, an, bn, tseg, nseg, nclasses, bp, k, jb_max, pval, pidx, nullptr);
+  dim3 grid(jb_max, ceil_div(bp, BM));
+  grouped_pairwise_kernel<EPI_ROWMIN><<<grid, 256, 0, s>>>(
+      a, b, an, bn, tseg, nseg, nclasses, bp, k, pval, pidx, nullptr);
   grouped_rowmin_combine_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pval, pidx, tseg, nseg, nclasses, bp, out_dist, out_idx);
 }
@@ -876,9 +777,9 @@ void launch_grouped_kde(const float* a, const float* b, const float* an,
                         const float* bn, const int* tseg, const int* nseg,
                         int nclasses, int bp, int k, int jb_max, float2* pkde,
                         float* out_lse, hipStream_t s) {
-  grouped_pairwise_kernel<EPI_KDE><<<grouped_grid(bp, jb_max), 256, 0, s>>>(
-      a, b, an, bn, tseg, nseg, nclasses, bp, k, jb_max, nullptr, nullptr,
-      pkde);
+  dim3 grid(jb_max, ceil_div(bp, BM));
+  grouped_pairwise_kernel<EPI_KDE><<<grid, 256, 0, s>>>(
+      a, b, an, bn, tseg, nseg, nclasses, bp, k, nullptr, nullptr, pkde);
   grouped_kde_combine_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pkde, tseg, nseg, nclasses, bp, out_lse);
 }
