@@ -452,12 +452,18 @@ def tknc_profile(layer_acts, k: int) -> torch.Tensor:
 
     ``layer_acts`` is a list of [N, K_l] tensors; columns are the flattened
     concatenation of layers (reference neuron_coverage.py:155-167).
+
+    The order is total, and the HIP kernel holds to the same one: descending
+    value with NaN greatest, then ascending column. Post-ReLU rows are
+    mostly exact zeros, so ties at the cut are the normal case; the
+    reference's argsort and ``torch.topk`` both leave them unspecified, a
+    stable descending sort does not.
     """
     parts = []
     for layer in layer_acts:
         flat = layer.reshape(layer.shape[0], -1)
         kk = min(k, flat.shape[1])
-        idx = torch.topk(flat, k=kk, dim=1).indices
+        idx = torch.sort(flat, dim=1, descending=True, stable=True).indices[:, :kk]
         prof = torch.zeros_like(flat, dtype=torch.bool)
         prof.scatter_(1, idx, True)
         parts.append(prof)

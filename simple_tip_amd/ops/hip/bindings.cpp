@@ -44,9 +44,6 @@ void launch_tknc(const float*, int, int, int, int, int, unsigned long long*,
                  hipStream_t);
 void launch_bucketize(const double*, const double*, int, int, int,
                       unsigned long long*, hipStream_t);
-void launch_cam_iteration(const unsigned long long*, int, int,
-                          unsigned long long*, unsigned char*, long long*,
-                          int*, long long*, hipStream_t);
 void launch_cam_greedy_coop(const unsigned long long*, int, int,
                             unsigned long long, unsigned char*,
                             unsigned long long*, long long*, int*, long long*,
@@ -490,8 +487,10 @@ torch::Tensor bucketize(torch::Tensor values, torch::Tensor thresholds,
   return words;
 }
 
-// Greedy CAM loop: device does all O(N*W) work, host only reads the picked
-// row per iteration. Returns the picked prefix (rows that added coverage).
+// Greedy CAM loop: the WHOLE loop runs in one persistent cooperative kernel
+// (64 resident blocks + software grid barriers; profiles/r02_cam_ladder.md),
+// whatever the mask width. The host reads the pick count and the picked
+// prefix (rows that added coverage) once at the end.
 torch::Tensor cam_greedy(torch::Tensor words, int64_t nbits) {
   TORCH_CHECK(words.is_cuda() && words.dtype() == torch::kInt64 &&
               words.dim() == 2 && words.is_contiguous());
@@ -501,83 +500,24 @@ torch::Tensor cam_greedy(torch::Tensor words, int64_t nbits) {
   const unsigned long long tail_mask =
       tail ? ((1ull << tail) - 1) : ~0ull;
   auto used = torch::zeros({rows}, opts.dtype(torch::kUInt8));
-  auto stream = cur_stream();
-
-  // Fast path: the WHOLE greedy loop in one persistent cooperative kernel
-  // (64 resident blocks + software grid barriers). The per-iteration
-  // two-kernel form paid ~200 us of dependent-launch latency per pick and
-  // a single-block loop is sweep-bound on one CU (~340 us/pick); this form
-  // has zero dispatch and a grid-parallel sweep (profiles/r02).
-  {
-    auto order_dev = torch::empty({rows}, opts);
-    auto n_dev = torch::zeros({1}, opts.dtype(torch::kInt32));
-    auto uncovered_dev = torch::empty({W}, opts);
-    auto part_val = torch::empty({64}, opts);
-    auto part_idx = torch::empty({64}, opts.dtype(torch::kInt32));
-    auto aux = torch::zeros({2}, opts.dtype(torch::kInt32));  // barrier, win
-    launch_cam_greedy_coop(
-        reinterpret_cast<const unsigned long long*>(
-            words.data_ptr<int64_t>()),
-        rows, W, tail_mask, used.data_ptr<uint8_t>(),
-        reinterpret_cast<unsigned long long*>(
-            uncovered_dev.data_ptr<int64_t>()),
-        reinterpret_cast<long long*>(part_val.data_ptr<int64_t>()),
-        part_idx.data_ptr<int>(),
-        reinterpret_cast<long long*>(order_dev.data_ptr<int64_t>()),
-        n_dev.data_ptr<int>(), aux.data_ptr<int>(),
-        aux.data_ptr<int>() + 1, stream);
-    const int n = n_dev.cpu().item<int>();
-    return order_dev.narrow(0, 0, n).cpu();
-  }
-
-  // Fallback (coverage mask too wide for LDS): per-iteration kernels with
-  // CHAIN iterations enqueued per host sync (iterations are idempotent
-  // once coverage is exhausted, so over-running is safe).
-  auto uncovered = torch::full({W}, -1, opts);  // all ones
-  if (tail)
-    uncovered.index_put_({W - 1}, (int64_t)tail_mask);
-  const int wpb = 8;
-  const int nblocks = (rows + wpb - 1) / wpb;
-  auto part_val = torch::empty({nblocks}, opts);
-  auto part_idx = torch::empty({nblocks}, opts.dtype(torch::kInt32));
-  constexpr int CHAIN = 256;
-  auto result = torch::empty({2 * CHAIN}, opts);
-  std::vector<int64_t> order;
-  order.reserve(std::min<int64_t>(rows, nbits));
-  std::vector<long long> host_result(2 * CHAIN);
-  bool done = false;
-  while (!done) {
-    for (int j = 0; j < CHAIN; ++j) {
-      launch_cam_iteration(
-          reinterpret_cast<const unsigned long long*>(
-              words.data_ptr<int64_t>()),
-          rows, W,
-          reinterpret_cast<unsigned long long*>(
-              uncovered.data_ptr<int64_t>()),
-          used.data_ptr<uint8_t>(),
-          reinterpret_cast<long long*>(part_val.data_ptr<int64_t>()),
-          part_idx.data_ptr<int>(),
-          reinterpret_cast<long long*>(result.data_ptr<int64_t>()) + 2 * j,
-          stream);
-    }
-    C10_HIP_CHECK(hipMemcpyAsync(host_result.data(),
-                                 result.data_ptr<int64_t>(),
-                                 2 * CHAIN * sizeof(long long),
-                                 hipMemcpyDeviceToHost, stream));
-    C10_HIP_CHECK(hipStreamSynchronize(stream));
-    for (int j = 0; j < CHAIN; ++j) {
-      if (host_result[2 * j] < 0) {
-        done = true;
-        break;
-      }
-      order.push_back(host_result[2 * j]);
-      if ((int64_t)order.size() >= rows) {
-        done = true;
-        break;
-      }
-    }
-  }
-  return torch::tensor(order, torch::dtype(torch::kInt64));
+  auto order_dev = torch::empty({rows}, opts);
+  auto n_dev = torch::zeros({1}, opts.dtype(torch::kInt32));
+  auto uncovered_dev = torch::empty({W}, opts);  // the kernel initialises it
+  auto part_val = torch::empty({64}, opts);
+  auto part_idx = torch::empty({64}, opts.dtype(torch::kInt32));
+  auto aux = torch::zeros({2}, opts.dtype(torch::kInt32));  // barrier, win
+  launch_cam_greedy_coop(
+      reinterpret_cast<const unsigned long long*>(words.data_ptr<int64_t>()),
+      rows, W, tail_mask, used.data_ptr<uint8_t>(),
+      reinterpret_cast<unsigned long long*>(
+          uncovered_dev.data_ptr<int64_t>()),
+      reinterpret_cast<long long*>(part_val.data_ptr<int64_t>()),
+      part_idx.data_ptr<int>(),
+      reinterpret_cast<long long*>(order_dev.data_ptr<int64_t>()),
+      n_dev.data_ptr<int>(), aux.data_ptr<int>(), aux.data_ptr<int>() + 1,
+      cur_stream());
+  const int n = n_dev.cpu().item<int>();
+  return order_dev.narrow(0, 0, n).cpu();
 }
 
 // All-pairs Levenshtein distance matrix (CPU, threaded) for the text

@@ -54,8 +54,17 @@ __global__ void profile_kernel(
         } else {  // KMNC: half-open k-section membership
           const int s = bit - col * sections;
           const float jump = (hi[col] - lo[col]) / sections;
-          const float b0 = lo[col] + jump * s;
-          const float b1 = lo[col] + jump * (s + 1);
+          // The oracle (fallback.kmnc_profile) rounds jump*s and the sum
+          // separately. Contracted into one v_fma_f32 the boundary moves by
+          // a last bit for some (lo, jump, s >= 3), and an activation that
+          // sits on it lands in the neighbouring section, so contraction is
+          // switched off for these two statements.
+          float b0, b1;
+          {
+#pragma clang fp contract(off)
+            b0 = lo[col] + jump * s;
+            b1 = lo[col] + jump * (s + 1);
+          }
           pred = (b0 <= a) && (a < b1);
         }
       }
@@ -81,8 +90,26 @@ __global__ void popcount_kernel(
 
 // TKNC: top-k (k<=4) neurons per layer, bits scattered at bit_offset+col.
 // One wave per row; each lane keeps a local sorted top-k over its strided
-// columns, then a wave tree-merge; ties prefer the lower column index
-// (torch.topk semantics).
+// columns, then a wave tree-merge.
+//
+// The order is total: descending value with NaN greatest (as torch.sort
+// ranks it) and -0.0 == 0.0, then ascending column -- the stable descending
+// sort fallback.tknc_profile uses. Each (value, column) pair becomes one
+// 64-bit key whose unsigned order is that order: the high word is the
+// float's bits made monotone, the low word is ~column. Key 0 would need the
+// bit pattern 0xffffffff, a NaN, and NaNs are canonicalised to the top, so 0
+// marks an empty slot below every real entry, -inf included.
+TIP_DEV unsigned long long tknc_key(float v, int c) {
+  unsigned int u = __float_as_uint(v);
+  if (v != v)
+    u = 0xffffffffu;  // NaN, either sign: above +inf
+  else if (v == 0.f)
+    u = 0x80000000u;  // -0.0 ranks with +0.0
+  else
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned int)~c;
+}
+
 __global__ void tknc_kernel(
     const float* __restrict__ layer,  // [rows, K]
     int rows, int K, int k, int bit_offset, int W,
@@ -92,65 +119,50 @@ __global__ void tknc_kernel(
   const int lane = lane_id();
   const float* arow = layer + (int64_t)row * K;
 
-  float tv[4];
-  int ti[4];
+  unsigned long long tk[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    tv[q] = -FLT_MAX;
-    ti[q] = 0x7fffffff;
-  }
+  for (int q = 0; q < 4; ++q) tk[q] = 0ull;
   for (int c = lane; c < K; c += WAVE) {
-    const float v = arow[c];
-    // insertion into the sorted (desc by v, asc by idx) quad
+    const unsigned long long key = tknc_key(arow[c], c);
+    // insertion into the descending quad (keys of distinct columns differ)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      if (v > tv[q] || (v == tv[q] && c < ti[q])) {
-        for (int r = 3; r > q; --r) {
-          tv[r] = tv[r - 1];
-          ti[r] = ti[r - 1];
-        }
-        tv[q] = v;
-        ti[q] = c;
+      if (key > tk[q]) {
+        for (int r = 3; r > q; --r) tk[r] = tk[r - 1];
+        tk[q] = key;
         break;
       }
     }
   }
   // wave merge: fold halves together
   for (int off = 32; off >= 1; off >>= 1) {
-    float ov[4];
-    int oi[4];
+    unsigned long long ok[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      ov[q] = __shfl_xor(tv[q], off);
-      oi[q] = __shfl_xor(ti[q], off);
-    }
+    for (int q = 0; q < 4; ++q) ok[q] = __shfl_xor(tk[q], off);
     // merge two sorted quads -> keep top 4
-    float mv[4];
-    int mi[4];
+    unsigned long long mk[4];
     int a = 0, b = 0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const bool take_a =
-          (tv[a] > ov[b]) || (tv[a] == ov[b] && ti[a] < oi[b]);
-      if (take_a) {
-        mv[q] = tv[a];
-        mi[q] = ti[a];
+      if (tk[a] >= ok[b]) {
+        mk[q] = tk[a];
         ++a;
       } else {
-        mv[q] = ov[b];
-        mi[q] = oi[b];
+        mk[q] = ok[b];
         ++b;
       }
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      tv[q] = mv[q];
-      ti[q] = mi[q];
-    }
+    for (int q = 0; q < 4; ++q) tk[q] = mk[q];
   }
   if (lane == 0) {
     for (int q = 0; q < k && q < K; ++q) {
-      const int bit = bit_offset + ti[q];
+      // the row's K real entries outrank every empty slot, so the first
+      // min(k, K) keys are real; the bound check keeps the store in the
+      // row's words even if that reasoning were ever broken
+      const unsigned int col = ~(unsigned int)tk[q];
+      if (col >= (unsigned int)K) continue;
+      const int bit = bit_offset + (int)col;
       atomicOr(&words[(int64_t)row * W + (bit >> 6)],
                1ull << (bit & 63));
     }
