@@ -5,7 +5,11 @@ stage-resident kernel against the chain of launches it replaces (same
 process, alternating, device events), and prints the achieved TB/s and TF
 of the stage kernels from the bytes and FLOPs their shapes need.
 
-Usage: python scripts/perf_fused_resnet.py [batch] [rounds]
+Usage: python scripts/perf_fused_resnet.py [batch] [rounds] [--stages-only]
+
+--stages-only runs nothing but the three stage kernels (one untimed round,
+then 10 calls per round after 2 warm-up calls): the short run to put under a profiler's counters,
+and the per-stage timing of an A/B comparison.
 """
 
 import statistics
@@ -58,16 +62,46 @@ STAGE_WORK = {
 }
 
 
+def stages_alone(fused, x, b, rounds):
+    """Time the three stage kernels alone, each on the plane before it."""
+    ext = fused.ext
+    p1, p2, p3 = fused.stage_params
+    plane1 = ext.resnet_stage1(x, p1)
+    plane2 = ext.resnet_stage2(plane1, p2)
+    calls = [
+        ("stage1", lambda: ext.resnet_stage1(x, p1)),
+        ("stage2", lambda: ext.resnet_stage2(plane1, p2)),
+        ("stage3", lambda: ext.resnet_stage3(plane2, p3)),
+    ]
+    times = {name: [] for name, _ in calls}
+    for name, fn in calls:  # one untimed round: clocks and caches settle
+        timeit(fn)
+    for _ in range(rounds):
+        for name, fn in calls:
+            times[name].append(timeit(fn))
+    for name, _ in calls:
+        ts = times[name]
+        ms = statistics.median(ts)
+        flops, nbytes = STAGE_WORK[name]
+        print(f"{name}: fused {ms:.3f} ms ({min(ts):.3f} - {max(ts):.3f}); "
+              f"{flops * b / ms / 1e9:.0f} TF, {nbytes * b / ms / 1e9:.2f} TB/s")
+
+
 def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    b = int(sys.argv[1]) if len(sys.argv) > 1 else 20480
-    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    argv = [a for a in sys.argv[1:] if a != "--stages-only"]
+    stages_only = "--stages-only" in sys.argv[1:]
+    b = int(argv[0]) if len(argv) > 0 else 20480
+    rounds = int(argv[1]) if len(argv) > 1 else 5
     model = fold_bn_inference(ResNet20()).to(dev)
     fused = FusedResNet20(model, dev)
     ext = fused.ext
     x = torch.randn(b, 32, 32, 3, device=dev)
     print(f"batch {b}, {rounds} alternating rounds of 10 calls")
+    if stages_only:
+        stages_alone(fused, x, b, rounds)
+        return
 
     # ---- the per-block chain, piece by piece ----
     def glue_in():
