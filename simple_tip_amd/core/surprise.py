@@ -244,6 +244,18 @@ class MultiModalSA(SA):
             sas[int(modal_id)] = sa_constructor(a, p)
         return MultiModalSA(discriminator, sas)
 
+    def fuse(self, device=None) -> "GroupedGaussianSA":
+        """Opt-in single-launch form of a Gaussian multimodal SA.
+
+        Allowed when every mode is an :class:`MDSA` or every mode is an
+        :class:`MLSA` (TypeError otherwise). The per-mode tables are stacked
+        once and every call scores all modes through
+        ``ops.grouped_gaussian_scores``: no Python loop over modes and, on
+        the GPU, no copy of the mode ids to the host. ``__call__`` of this
+        object is unchanged.
+        """
+        return GroupedGaussianSA(self, device=device)
+
     def __call__(self, activations, predictions=None, num_threads: int = 1):
         acts = _flatten_layers(activations)
         preds = None if predictions is None else _class_predictions(predictions)
@@ -756,3 +768,167 @@ class DSA(SA):
             self._fused_prio = fp
         dsa, _ = fp(target_ats.float(), target_pred)
         return dsa
+
+
+class GroupedGaussianSA(SA):
+    """All modes of a Gaussian :class:`MultiModalSA` scored in one op call
+    (``MultiModalSA.fuse``): pc-MDSA / pc-MMDSA (every mode an MDSA) as
+    Mahalanobis forms, pc-MLSA (every mode an MLSA) as mixture NLLs.
+
+    The tables are stacked once from the fp64 fits: MDSA contributes its mean
+    and precision, MLSA its means, ``M = P P^T`` and ``logc = log w +
+    sum(log diag P) - D/2 log 2 pi`` per component, all formed in fp64. On a
+    GPU device they are cast to fp32 (the kernel's dtype); on the CPU they
+    stay fp64, so the fused CPU result equals the per-mode loop to rounding.
+    Mode ids are compacted to groups ``0..G-1`` through a lookup tensor on
+    the device; an id without a fitted mode maps to group -1 and scores
+    ``+inf``.
+
+    ``check_unseen`` keeps the per-mode semantics for such ids (UserWarning,
+    or ValueError in strict mode). The check is one device reduction whose
+    result is read on the host; with ``check_unseen=False`` a GPU call makes
+    no device-to-host copy at all (unseen ids still score ``+inf``).
+    """
+
+    def __init__(self, multimodal: "MultiModalSA", device=None, check_unseen: bool = True):
+        sas = multimodal.modal_sa
+        kinds = {type(sa) for sa in sas.values()}
+        if not sas or kinds not in ({MDSA}, {MLSA}):
+            raise TypeError(
+                "fuse() needs every mode to be an MDSA or every mode to be "
+                f"an MLSA, got {sorted(k.__name__ for k in kinds)}"
+            )
+        self.is_mixture = kinds == {MLSA}
+        self.discriminator = multimodal.discriminator
+        self.by_class = self.discriminator is _by_class_discriminator
+        self.check_unseen = bool(check_unseen)
+        modes = sorted(int(m) for m in sas)
+        if modes[0] < 0:
+            raise ValueError("mode ids must be >= 0")
+        if device is None:
+            first = getattr(sas[modes[0]], "device", None)
+            device = first if first is not None else "cpu"
+        self.device = torch.device(device)
+        on_gpu = self.device.type == "cuda"
+
+        means, mats, logc, off = [], [], [], [0]
+        for m in modes:
+            sa = sas[m]
+            if self.is_mixture:
+                mu = sa.means.detach().cpu().double()
+                p = sa.prec_chol.detach().cpu().double()
+                d = mu.shape[1]
+                means.append(mu)
+                mats.append(p @ p.transpose(1, 2))
+                logc.append(
+                    sa.log_weights.detach().cpu().double()
+                    + torch.log(torch.diagonal(p, dim1=1, dim2=2)).sum(dim=1)
+                    - 0.5 * d * np.log(2 * np.pi)
+                )
+                off.append(off[-1] + mu.shape[0])
+            else:
+                prec = sa.precision.detach().cpu().double()
+                means.append(sa.mean.detach().cpu().double().unsqueeze(0))
+                # pinv(hermitian=True) is symmetric up to rounding; the
+                # kernel reads rows as columns, so make it exact
+                mats.append((0.5 * (prec + prec.t())).unsqueeze(0))
+                off.append(off[-1] + 1)
+        dt = torch.float32 if on_gpu else torch.float64
+        self.means = torch.cat(means).to(self.device, dt).contiguous()
+        self.mats = torch.cat(mats).to(self.device, dt).contiguous()
+        self.logc = (
+            torch.cat(logc).to(self.device, dt).contiguous()
+            if self.is_mixture
+            else None
+        )
+        self.comp_off = torch.tensor(off, dtype=torch.int32)  # host table
+        self.num_groups = len(modes)
+        lookup = torch.full((modes[-1] + 1,), -1, dtype=torch.int64)
+        lookup[torch.tensor(modes)] = torch.arange(len(modes))
+        self.lookup = lookup.to(self.device)
+        #: mode id == group id, so a plan made from the ids is a plan of the
+        #: groups (the serving path reuses its class plan then)
+        self.identity_groups = modes == list(range(len(modes)))
+        self._tables = None
+
+    def tables(self, device=None):
+        """Validated fp32 device tables of the HIP path (built on first use)."""
+        device = torch.device(self.device if device is None else device)
+        if self._tables is None or self._tables.device != device:
+            from ..ops import hip_ops
+
+            self._tables = hip_ops.GaussianTables(
+                self.comp_off, self.means.float(), self.mats.float(),
+                None if self.logc is None else self.logc.float(), device,
+            )
+        return self._tables
+
+    def mode_ids(self, x: torch.Tensor, predictions) -> torch.Tensor:
+        """Mode id per row, on ``x``'s device."""
+        if self.by_class:
+            if x.is_cuda:
+                p = predictions
+                if not isinstance(p, torch.Tensor):
+                    p = torch.as_tensor(np.asarray(p))
+                assert p.dim() == 1, "Class predictions must be one-dimensional"
+                return p.to(x.device).long()
+            return _class_predictions(predictions).to(x.device)
+        if isinstance(self.discriminator, _KmeansDiscriminator):
+            centers = self.discriminator.best_centers
+            return kmeans_predict(x.float(), centers.to(x.device)).long()
+        ids = self.discriminator(x, predictions)
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.as_tensor(np.asarray(ids))
+        return ids.to(x.device).long()
+
+    def groups_of(self, ids: torch.Tensor) -> torch.Tensor:
+        """Group per mode id (-1 for ids without a fitted mode)."""
+        if self.lookup.device != ids.device:
+            self.lookup = self.lookup.to(ids.device)  # once per device
+        n_ids = self.lookup.shape[0]
+        inside = (ids >= 0) & (ids < n_ids)
+        return torch.where(
+            inside, self.lookup[ids.clamp(0, n_ids - 1)], torch.full_like(ids, -1)
+        )
+
+    def _check_unseen(self, ids, group):
+        if not self.check_unseen or not bool((group < 0).any()):
+            return
+        missing = torch.unique(ids[group < 0]).tolist()
+        if _STRICT_MODES:
+            raise ValueError(
+                f"No modal found for modal id {missing[0]} (reference raises here)"
+            )
+        for modal_id in missing:
+            warnings.warn(
+                f"No modal found for modal id {modal_id}; scoring those "
+                f"inputs as maximally surprising (+inf).",
+                UserWarning,
+            )
+
+    def __call__(self, activations, predictions=None, num_threads: int = 1):
+        acts = _flatten_layers(activations)
+        if acts.shape[0] == 0:
+            return torch.empty(0)
+        if self.device.type == "cuda" or acts.is_cuda:
+            dev = acts.device if acts.is_cuda else self.device
+            x = acts.to(dev)
+            if x.dtype != torch.bfloat16:
+                x = x.float()
+        else:
+            x = acts.double()
+        ids = self.mode_ids(x, predictions)
+        assert ids.shape[0] == x.shape[0], "discriminator length mismatch"
+        group = self.groups_of(ids)
+        self._check_unseen(ids, group)
+        if ops._route(x) is ops.fallback:
+            return ops.fallback.grouped_gaussian_scores(
+                x.to(self.mats.dtype), group, self.comp_off,
+                self.means.to(x.device), self.mats.to(x.device),
+                None if self.logc is None else self.logc.to(x.device),
+            )
+        from ..ops import hip_ops
+
+        return hip_ops.grouped_gaussian_scores_tables(
+            x, group, self.tables(x.device)
+        )

@@ -22,12 +22,12 @@ rounding (rank correlation > 0.99 vs fp32, pinned by test).
 """
 
 import os
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
-from ..core.surprise import DSA, LSA, MultiModalSA
+from ..core.surprise import DSA, LSA, GroupedGaussianSA, MultiModalSA
 from ..ops import _load_compiled
 
 
@@ -41,6 +41,10 @@ class FusedPrioritizer:
     (min, argmin) / logsumexp results merge with deterministic rank-ordered
     reductions over RCCL (parallel/sharded.py semantics), so sharded scores
     equal single-device ones.
+
+    ``gaussian`` adds Gaussian scorers (pc-MDSA / pc-MLSA / pc-MMDSA as
+    ``MultiModalSA`` of MDSA or MLSA modes) served by :meth:`score_all`
+    through the grouped Gaussian kernels; ``__call__`` is unaffected.
     """
 
     def __init__(
@@ -50,9 +54,21 @@ class FusedPrioritizer:
         device,
         pairwise_dtype=None,
         fast: Optional[bool] = None,
+        gaussian: Optional[Dict[str, MultiModalSA]] = None,
     ):
         self.ext = _load_compiled()
         self.device = device
+        # Gaussian scorers served by score_all(): each MultiModalSA of MDSA /
+        # MLSA modes is fuse()d here once. Serving follows the DSA / LSA rule
+        # for ids without a fitted mode (+inf, no host check), so a call
+        # stays free of device-to-host copies.
+        self.gaussian: Dict[str, GroupedGaussianSA] = {}
+        for name, sa in (gaussian or {}).items():
+            if name in ("dsa", "pc-lsa"):
+                raise ValueError(f"gaussian scorer name {name!r} is reserved")
+            self.gaussian[name] = (
+                sa if isinstance(sa, GroupedGaussianSA) else sa.fuse(device=device)
+            )
         if dsa._class_cache is None:
             dsa._build_class_cache()
         self.num_classes = dsa.num_classes
@@ -296,7 +312,83 @@ class FusedPrioritizer:
         self._ws[(b, d_at)] = ws
         return ws
 
-    def _fast_call(self, ats, pred):
+    def _gaussian_launch(self, ats, pred, plan, main_stream):
+        """Enqueue every Gaussian scorer on the Gaussian side stream, ordered
+        after what the main stream holds now (the segment plan, on the fast
+        path). Returns the [names, B] score tensor; the caller makes the main
+        stream wait on the side stream before handing anything out, which is
+        also what lets the next call reuse the scorers' workspaces.
+
+        ``plan`` is the call's (tseg, rowmap) over the predicted classes or
+        None. A by-class scorer whose groups are the classes reuses it; a
+        kmeans-discriminated one (or one with other groups, or a batch over
+        the workspace cap) plans from its own group ids."""
+        from ..ops import hip_ops
+
+        names = list(self.gaussian)
+        x = ats if ats.dtype == torch.bfloat16 else ats.float()
+        x = x.contiguous()
+        out = torch.full(
+            (len(names), ats.shape[0]), float("inf"),
+            dtype=torch.float32, device=ats.device,
+        )
+        if not hasattr(self, "_gauss_stream"):
+            self._gauss_stream = torch.cuda.Stream()
+        ready = torch.cuda.Event()
+        ready.record(main_stream)
+        # x may be a temporary of the main stream's pool: keep its memory
+        # from being handed out again before the side stream has read it
+        x.record_stream(self._gauss_stream)
+        with torch.cuda.stream(self._gauss_stream):
+            self._gauss_stream.wait_event(ready)
+            for k, name in enumerate(names):
+                sa = self.gaussian[name]
+                tables = sa.tables(ats.device)
+                if (
+                    plan is not None
+                    and sa.by_class
+                    and sa.identity_groups
+                    and tables.G == self.num_classes
+                    and ats.shape[0] <= tables.chunk_rows()
+                ):
+                    hip_ops.grouped_gaussian_into(
+                        x, tables, plan[0], plan[1], out[k]
+                    )
+                else:
+                    group = sa.groups_of(sa.mode_ids(x, pred))
+                    hip_ops.grouped_gaussian_scores_tables(
+                        x, group, tables, out=out[k]
+                    )
+        return out
+
+    @torch.no_grad()
+    def score_all(
+        self, ats: torch.Tensor, pred: torch.Tensor
+    ) -> Dict[str, torch.Tensor]:
+        """Every served score of one batch: ``"dsa"``, ``"pc-lsa"`` (when an
+        LSA was fitted) and one entry per ``gaussian`` scorer. ``"dsa"`` /
+        ``"pc-lsa"`` are what ``__call__`` returns; a Gaussian entry equals
+        ``fuse()(ats, pred)`` of its scorer. The Gaussian kernels stay exact
+        fp32 in bf16 mode and overlap the DSA / LSA kernels on a side
+        stream."""
+        if not self.gaussian:
+            dsa, lsa = self(ats, pred)
+            gauss = None
+        elif self.fast and ats.is_cuda:
+            dsa, lsa, gauss = self._fast_call(ats, pred, with_gaussian=True)
+        else:
+            main_stream = torch.cuda.current_stream()
+            gauss = self._gaussian_launch(ats, pred, None, main_stream)
+            dsa, lsa = self(ats, pred)
+            main_stream.wait_stream(self._gauss_stream)
+        res = {"dsa": dsa}
+        if lsa is not None:
+            res["pc-lsa"] = lsa
+        for k, name in enumerate(self.gaussian):
+            res[name] = gauss[k]
+        return res
+
+    def _fast_call(self, ats, pred, with_gaussian: bool = False):
         b, d_at = ats.shape
         assert d_at == self.trainS16.shape[1], "AT width differs from the fit"
         ext, ws = self.ext, self._workspaces(b, d_at)
@@ -311,6 +403,11 @@ class FusedPrioritizer:
             (2, b), float("inf"), dtype=torch.float32, device=ats.device
         )
         main_stream = torch.cuda.current_stream()
+        gauss = None
+        if with_gaussian:
+            gauss = self._gaussian_launch(
+                ats, pred, (ws["tseg"], ws["rowmap"]), main_stream
+            )
         if self.lsa_ready:
             assert self._keep_cols <= d_at
             if not hasattr(self, "_lsa_stream"):
@@ -338,8 +435,11 @@ class FusedPrioritizer:
         )
         if self.lsa_ready:
             main_stream.wait_stream(self._lsa_stream)
-            return out[0], out[1]
-        return out[0], None
+        lsa_out = out[1] if self.lsa_ready else None
+        if with_gaussian:
+            main_stream.wait_stream(self._gauss_stream)
+            return out[0], lsa_out, gauss
+        return out[0], lsa_out
 
     def _lsa_lse(self, padded, bp, tseg_cpu, tseg):
         """Per-class whiten GEMMs + one grouped KDE launch (+ cross-rank

@@ -7,6 +7,7 @@ on device; SA hot loops route through the MFMA pairwise kernel via ops.
 """
 
 import logging
+import os
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -36,6 +37,9 @@ class SurpriseHandler:
         ),
     }
 
+    #: the Gaussian configurations MultiModalSA.fuse() applies to
+    FUSABLE_SA = ("pc-mdsa", "pc-mlsa", "pc-mmdsa")
+
     def __init__(
         self,
         model,
@@ -44,9 +48,20 @@ class SurpriseHandler:
         device=None,
         predict_batch: int = 512,
         dist_shard: bool = False,
+        modal_sa_mode: str = "per_mode",
     ):
         from ..parallel.dist import get_world_size
 
+        # "fused": the three Gaussian configurations (pc-mdsa, pc-mlsa,
+        # pc-mmdsa) are fit as usual and then MultiModalSA.fuse()d, so every
+        # evaluation scores all modes in one grouped launch. "per_mode" (the
+        # default) keeps the per-mode loop. TIP_MODAL_SA_MODE overrides.
+        modal_sa_mode = os.environ.get("TIP_MODAL_SA_MODE", modal_sa_mode)
+        if modal_sa_mode not in ("per_mode", "fused"):
+            raise ValueError(
+                f"modal_sa_mode must be 'per_mode' or 'fused', got {modal_sa_mode!r}"
+            )
+        self.modal_sa_mode = modal_sa_mode
         self.sa_layers = list(sa_layers)
         # dist_shard: shard AT-extraction and SA scoring over the test-input
         # axis across ranks (DP per SURVEY §2.4); train ATs are extracted
@@ -112,6 +127,8 @@ class SurpriseHandler:
                 sa = sa_func(self.train_ats, self.train_pred)
                 if isinstance(sa, DSA) and dsa_badge_size is not None:
                     sa.badge_size = dsa_badge_size
+                if self.modal_sa_mode == "fused" and sa_name in self.FUSABLE_SA:
+                    sa = sa.fuse(device=self.train_ats.device)
             setup_time = self.train_at_timer.get() + setup_timer.get()
 
             for ds_name, (test_ats, test_pred, pred_time, n) in test_apt.items():

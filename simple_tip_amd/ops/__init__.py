@@ -104,6 +104,35 @@ def kde_logsumexp(test_w: torch.Tensor, train_w: torch.Tensor) -> torch.Tensor:
     return _route(test_w).kde_logsumexp(test_w.contiguous(), train_w.contiguous())
 
 
+def grouped_gaussian_scores(
+    x: torch.Tensor,
+    group: torch.Tensor,
+    comp_off: torch.Tensor,
+    means: torch.Tensor,
+    mats: torch.Tensor,
+    logc: torch.Tensor = None,
+) -> torch.Tensor:
+    """Gaussian scores [N] of rows ``x[n]`` under the components of group
+    ``group[n]``, all groups in one pass.
+
+    ``means`` [J, D] and ``mats`` [J, D, D] (symmetric precision matrices)
+    stack the components of all G groups; group ``g`` owns components
+    ``comp_off[g] .. comp_off[g+1]`` (``comp_off`` int32 [G+1]). With
+    ``q_j = (x - mu_j)^T M_j (x - mu_j)``: ``logc=None`` is the Mahalanobis
+    form of the group's single component, otherwise the mixture NLL
+    ``-logsumexp_j(logc_j - q_j / 2)``. Rows whose group id is outside
+    ``[0, G)`` score ``+inf``.
+
+    On GPU tensors (fp32 or bf16 ``x``, fp32 tables) one exact-fp32 MFMA
+    launch covers every group and the result is float32; a row's score does
+    not depend on the batch it arrives in. Outside the envelope (more than
+    256 groups, more than 8 components in a group, non-contiguous ``mats``)
+    the call raises ValueError, it never falls back. CPU tensors compute in
+    the dtype of ``mats``.
+    """
+    return _route(x).grouped_gaussian_scores(x, group, comp_off, means, mats, logc)
+
+
 # --- score / profile ops ----------------------------------------------------
 
 def softmax_uncertainties(probs: torch.Tensor) -> Dict[str, torch.Tensor]:

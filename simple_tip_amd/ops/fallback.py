@@ -534,3 +534,103 @@ def segment_plan(
     dest = torch.full((b,), -1, dtype=torch.int32, device=p.device)
     dest[order] = where.to(torch.int32)
     return tseg.to(torch.int32), rowmap, dest
+
+
+# ---------------------------------------------------------------------------
+# Grouped Gaussian scoring (pc-MDSA / pc-MLSA / pc-MMDSA)
+# ---------------------------------------------------------------------------
+
+GAUSS_MAX_GROUPS = 256  # what one segment plan addresses
+GAUSS_MAX_SLOTS = 8     # components per group
+
+
+def gaussian_check_envelope(comp_off, means, mats, logc):
+    """Validate grouped-Gaussian tables; returns ``(G, J, D, max_slots)``.
+
+    ``comp_off`` is read on the host (it is a fit-time table, so this is done
+    once per table set, not per call). Raises ValueError outside the
+    envelope: more than 256 groups, more than 8 components in a group, a
+    non-contiguous ``mats``, or Mahalanobis mode (``logc is None``) with a
+    group that does not have exactly one component.
+    """
+    if means.dim() != 2 or mats.dim() != 3:
+        raise ValueError("expected means [J, D] and mats [J, D, D]")
+    J, D = means.shape
+    if tuple(mats.shape) != (J, D, D):
+        raise ValueError(f"mats must be [{J}, {D}, {D}], got {tuple(mats.shape)}")
+    if not mats.is_contiguous():
+        raise ValueError("mats must be contiguous")
+    off = torch.as_tensor(comp_off).detach().cpu().to(torch.int64)
+    if off.dim() != 1 or off.numel() < 2:
+        raise ValueError("comp_off must be [G+1] with G >= 1")
+    G = off.numel() - 1
+    if G > GAUSS_MAX_GROUPS:
+        raise ValueError(
+            f"grouped_gaussian_scores supports up to {GAUSS_MAX_GROUPS} "
+            f"groups (got {G})"
+        )
+    counts = off[1:] - off[:-1]
+    if int(off[0]) != 0 or int(off[-1]) != J or bool((counts < 0).any()):
+        raise ValueError("comp_off must ascend from 0 to J")
+    smax = int(counts.max())
+    if smax > GAUSS_MAX_SLOTS:
+        raise ValueError(
+            f"grouped_gaussian_scores supports up to {GAUSS_MAX_SLOTS} "
+            f"components per group (got {smax})"
+        )
+    if logc is None:
+        if bool((counts != 1).any()):
+            raise ValueError(
+                "Mahalanobis mode (logc=None) needs exactly one component "
+                "per group"
+            )
+    elif logc.dim() != 1 or logc.shape[0] != J:
+        raise ValueError("logc must be [J]")
+    return G, J, D, smax
+
+
+def grouped_gaussian_scores(
+    x: torch.Tensor,
+    group: torch.Tensor,
+    comp_off: torch.Tensor,
+    means: torch.Tensor,
+    mats: torch.Tensor,
+    logc: torch.Tensor = None,
+) -> torch.Tensor:
+    """Per-row Gaussian score of ``x[n]`` under the components of group
+    ``group[n]`` (components ``comp_off[g] .. comp_off[g+1]``).
+
+    With ``q_j(x) = (x - mu_j)^T M_j (x - mu_j)``: ``logc is None`` gives the
+    Mahalanobis form ``q`` of the group's single component, otherwise the
+    mixture NLL ``-logsumexp_j(logc_j - q_j / 2)``. Rows whose group id is
+    outside ``[0, G)`` and rows of a group without components score ``+inf``.
+    Computes in the dtype of ``mats`` (a float64 call is the test oracle of
+    the HIP kernels) and returns that dtype.
+    """
+    G, J, D, smax = gaussian_check_envelope(comp_off, means, mats, logc)
+    dt = mats.dtype
+    dev = x.device
+    if x.dim() != 2 or x.shape[1] != D:
+        raise ValueError(f"x must be [N, {D}]")
+    xs = x.to(dt)
+    mu = means.to(dev, dt)
+    mm = mats.to(dev)
+    lc = None if logc is None else logc.to(dev, dt)
+    grp = group.to(dev, torch.int64)
+    off = torch.as_tensor(comp_off).cpu().to(torch.int64).tolist()
+    n = xs.shape[0]
+    # t[n, s]: log-term of slot s (or q itself in Mahalanobis mode)
+    t = torch.full((n, max(smax, 1)), -float("inf"), dtype=dt, device=dev)
+    for g in range(G):
+        rows = torch.nonzero(grp == g, as_tuple=True)[0]
+        if rows.numel() == 0:
+            continue
+        for s, j in enumerate(range(off[g], off[g + 1])):
+            d = xs[rows] - mu[j]
+            q = ((d @ mm[j]) * d).sum(dim=1)
+            t[rows, s] = q if lc is None else lc[j] - 0.5 * q
+    if lc is None:
+        out = t[:, 0].clone()
+        out[torch.isneginf(out)] = float("inf")  # unplaced / empty group
+        return out
+    return -torch.logsumexp(t, dim=1)

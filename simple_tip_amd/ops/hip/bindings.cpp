@@ -87,6 +87,13 @@ void launch_grouped_kde_plan(const short*, const short*, const float*,
                              const float*, const int*, const int*, const int*,
                              int, const int*, const float*, int, int, int, int,
                              float2*, float*, hipStream_t);
+void launch_grouped_center(const void*, bool, int, int, const int*, const int*,
+                           const int*, int, int, const float*, int, float*,
+                           hipStream_t);
+int grouped_gauss_max_slots();
+void launch_grouped_gauss_plan(const float*, const float*, const int*,
+                               const int*, const int*, int, const float*, int,
+                               int, int, int, float*, float*, hipStream_t);
 int mc_dropout_max_grid(int, int);
 int mc_dropout_rows_per_block();
 int mc_dropout_max_classes();
@@ -396,6 +403,63 @@ void grouped_kde_plan(torch::Tensor white, torch::Tensor wtrain,
       cls_const.data_ptr<float>(), c, bp, d, jb_max,
       reinterpret_cast<float2*>(pkde.data_ptr<float>()),
       out_lsa.data_ptr<float>(), cur_stream());
+}
+
+// Grouped Gaussian scores through a segment plan made from the group ids:
+// centre (segment.hip), quadratic forms + final scores (pairwise.hip). `out`
+// must be pre-filled with +inf; rows the plan places nowhere keep it. With
+// `logc` the score is the mixture NLL, without it the Mahalanobis form of the
+// group's single component. `slots` is the largest component count of any
+// group (a host constant of the tables, so nothing is read back here).
+void grouped_gauss_plan(torch::Tensor x, torch::Tensor tseg,
+                        torch::Tensor rowmap, torch::Tensor comp_off,
+                        torch::Tensor means, torch::Tensor mats,
+                        c10::optional<torch::Tensor> logc, int64_t slots,
+                        torch::Tensor dc, torch::Tensor pquad,
+                        torch::Tensor out) {
+  TORCH_CHECK(x.dim() == 2 && means.dim() == 2 && mats.dim() == 3,
+              "expected x [B, D], means [J, D], mats [J, D, D]");
+  const int64_t b = x.size(0), d = x.size(1), j = means.size(0);
+  const int64_t g = tseg.numel() - 1;
+  const int64_t bp = segment_plan_rows(b, g);
+  const int64_t jb = (d + kBN - 1) / kBN;
+  TORCH_CHECK(b >= 1 && d >= 1 && j >= 1 && g >= 1, "empty operand");
+  TORCH_CHECK(slots >= 1 && slots <= grouped_gauss_max_slots(),
+              "at most ", grouped_gauss_max_slots(), " components per group");
+  TORCH_CHECK(j * d < (1ll << 31) && slots * bp < (1ll << 31),
+              "operand too large");
+  const bool bf16 = x.scalar_type() == torch::kBFloat16;
+  check_dev(x, bf16 ? torch::kBFloat16 : torch::kFloat32, b * d, "x");
+  check_dev(tseg, torch::kInt32, g + 1, "tseg");
+  check_dev(rowmap, torch::kInt32, bp, "rowmap");
+  check_dev(comp_off, torch::kInt32, g + 1, "comp_off");
+  check_dev(means, torch::kFloat32, j * d, "means");
+  check_dev(mats, torch::kFloat32, j * d * d, "mats");
+  check_dev(dc, torch::kFloat32, slots * bp * d, "dc");
+  check_dev(pquad, torch::kFloat32, slots * jb * bp, "pquad");
+  check_dev(out, torch::kFloat32, b, "out");
+  const float* lc = nullptr;
+  if (logc.has_value()) {
+    check_dev(logc.value(), torch::kFloat32, j, "logc");
+    lc = logc.value().data_ptr<float>();
+  }
+  if (d % 4 == 0) {
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % (bf16 ? 8 : 16) ==
+                        0 &&
+                    reinterpret_cast<uintptr_t>(means.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(mats.data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(dc.data_ptr()) % 16 == 0,
+                "operands must be 16-byte aligned");
+  }
+  launch_grouped_center(x.data_ptr(), bf16, b, d, rowmap.data_ptr<int>(),
+                        tseg.data_ptr<int>(), comp_off.data_ptr<int>(), g, bp,
+                        means.data_ptr<float>(), slots, dc.data_ptr<float>(),
+                        cur_stream());
+  launch_grouped_gauss_plan(dc.data_ptr<float>(), mats.data_ptr<float>(),
+                            tseg.data_ptr<int>(), comp_off.data_ptr<int>(),
+                            rowmap.data_ptr<int>(), b, lc, g, bp, d, slots,
+                            pquad.data_ptr<float>(), out.data_ptr<float>(),
+                            cur_stream());
 }
 
 torch::Tensor kde_logsumexp(torch::Tensor test, torch::Tensor train) {
@@ -819,6 +883,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_whiten_max_features", &grouped_whiten_max_features);
   m.def("grouped_rowmin_plan", &grouped_rowmin_plan);
   m.def("grouped_kde_plan", &grouped_kde_plan);
+  m.def("grouped_gauss_plan", &grouped_gauss_plan, py::arg("x"),
+        py::arg("tseg"), py::arg("rowmap"), py::arg("comp_off"),
+        py::arg("means"), py::arg("mats"), py::arg("logc"), py::arg("slots"),
+        py::arg("dc"), py::arg("pquad"), py::arg("out"));
+  m.def("grouped_gauss_max_slots", &grouped_gauss_max_slots);
   m.def("profile", &profile);
   m.def("pack_bits", &pack_bits);
   m.def("popcount_rows", &popcount_rows);

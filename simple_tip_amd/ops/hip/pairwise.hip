@@ -25,6 +25,9 @@
 //   fold_rowmin/fold_kde fold the column-block partials of one row, bj
 //                        ascending; all six combine kernels call them
 //   class_of_row         class of a padded row from the segment table
+//   tile_epilogue_quad   EPI_QUAD: per-row sum of (tile .* centred row), for
+//                        grouped_quad_kernel (Gaussian quadratic forms); it
+//                        shares the main loop and merge_halves_store
 // pairwise_kernel (flat: XCD swizzle, EPI_FULL) and grouped_pairwise_kernel
 // (class segments) differ only in how a block finds its tile and its bounds,
 // so a grouped result equals the per-class flat result bit for bit, and the
@@ -45,7 +48,7 @@ constexpr int BN = 128;
 constexpr int BK = 32;
 constexpr int LDS_PAD = 4;  // pad k-major rows to de-conflict staging writes
 
-enum Epilogue { EPI_FULL = 0, EPI_ROWMIN = 1, EPI_KDE = 2 };
+enum Epilogue { EPI_FULL = 0, EPI_ROWMIN = 1, EPI_KDE = 2, EPI_QUAD = 3 };
 
 // Staging is split T14-style (issue-early / write-late): the global loads
 // for tile t+1 are issued into registers BEFORE tile t's MFMA loop (HBM
@@ -175,6 +178,9 @@ TIP_DEV void merge_halves_store(
           MinIdx{red_v[r][0], red_i[r][0]}, MinIdx{red_v[r][1], red_i[r][1]});
       pmin_val[(int64_t)bj * stride + i] = best.v;
       pmin_idx[(int64_t)bj * stride + i] = best.i;
+    } else if (EPI == EPI_QUAD) {
+      // plain sum, low half first; the partial goes where ROWMIN's value does
+      pmin_val[(int64_t)bj * stride + i] = red_v[r][0] + red_v[r][1];
     } else {
       pkde[(int64_t)bj * stride + i] =
           kde_merge_pair(red_v[r][0], red_s[r][0], red_v[r][1], red_s[r][1]);
@@ -258,6 +264,48 @@ TIP_DEV void tile_epilogue_f32(
   __syncthreads();
   merge_halves_store<EPI>(red_v, red_i, red_s, row0, row_end, stride, bj,
                           pmin_val, pmin_idx, pkde);
+}
+
+// EPI_QUAD epilogue of the block tile at (row0, col0), for A = centred rows
+// d [row_end, ncols] and B = one symmetric matrix M: the tile holds (d.M) and
+// the row's partial quadratic form is sum_j (d.M)[r][j] * d[r][j] over the
+// tile's columns. `a` is the matrix-local origin of d (row i, local column j
+// at a[i * ncols + j]); lcol0 is the tile's first local column. Columns at
+// or past ncols contribute zero (their accumulators are zero as well: B
+// staged zeros there). Same C/D layout as tile_epilogue_f32. Summation
+// order is fixed: n = 0 then n = 1 in the lane, the 32-lane xor tree, the
+// low 64-column half before the high one.
+TIP_DEV void tile_epilogue_quad(
+    const TileAcc& acc, const float* __restrict__ a, int ncols, int row0,
+    int row_end, int lcol0, int stride, int bj, float (*red_v)[2],
+    float* __restrict__ pquad) {
+  const int lane = lane_id();
+  const int wr = wave_id() >> 1;
+  const int wc = wave_id() & 1;
+  const int jl0 = lcol0 + wc * 64 + (lane & 31);  // n=0 local column
+  const bool ok0 = jl0 < ncols;
+  const bool ok1 = jl0 + 32 < ncols;
+
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+      const int row_local = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+      const int block_row = wr * 64 + m * 32 + row_local;
+      const int i = row0 + block_row;
+      const bool row_ok = i < row_end;
+      const float* ar = a + (int64_t)(row_ok ? i : 0) * ncols;
+      const float d0 = (row_ok && ok0) ? ar[jl0] : 0.f;
+      const float d1 = (row_ok && ok1) ? ar[jl0 + 32] : 0.f;
+      float s = acc.t[m][0][reg] * d0;
+      s += acc.t[m][1][reg] * d1;
+      s = half_reduce_sum(s);
+      if ((lane & 31) == 0) red_v[block_row][wc] = s;
+    }
+  }
+  __syncthreads();
+  merge_halves_store<EPI_QUAD>(red_v, nullptr, nullptr, row0, row_end, stride,
+                               bj, pquad, nullptr, nullptr);
 }
 
 // Class of padded row `row`: the last class whose segment starts at or
@@ -349,6 +397,98 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_kernel(
   tile_epilogue_f32<EPI>(acc, anorm, bnorm, row0, Bp, col0, ncol1, Bp, bj,
                          red_v, red_i, red_s, nullptr, pmin_val, pmin_idx,
                          pkde);
+}
+
+// ---------------------------------------------------------------------------
+// Grouped Gaussian quadratic forms (pc-MDSA / pc-MLSA / pc-MMDSA scoring).
+// Padded row p of group g holds, per component slot s, the centred row
+// dc[s][p][:] = x - mean[comp_off[g] + s] (segment.hip). The "train side" is
+// the stack of all precision matrices, mats [J * D, D]: each is symmetric,
+// so its rows are its columns and the tile of A.B^T against rows
+// [j * D, (j + 1) * D) is (d . M_j). Grid: x = column blocks of D, y = row
+// blocks of the padded batch, z = component slot. Exact fp32 only (the
+// dynamic range of near-singular precisions is not validated for bf16
+// operands). Partials: pquad[(s * gridDim.x + bj) * Bp + p].
+// ---------------------------------------------------------------------------
+
+__launch_bounds__(256, 2) __global__ void grouped_quad_kernel(
+    const float* __restrict__ dc,        // [S, Bp, D] centred rows
+    const float* __restrict__ mats,      // [J * D, D] symmetric matrices
+    const int* __restrict__ tseg,        // [G+1] padded row offsets (x128)
+    const int* __restrict__ comp_off,    // [G+1] first component of a group
+    int ngroups, int Bp, int D,
+    float* __restrict__ pquad) {         // [S, jb, Bp]
+  __shared__ float lds[2 * BK * (BM + LDS_PAD)];
+  __shared__ float red_v[BM][2];
+
+  const int bj = blockIdx.x;
+  const int row0 = blockIdx.y * BM;
+  const int s = blockIdx.z;
+  if (row0 >= Bp || row0 >= tseg[ngroups]) return;
+  const int g = class_of_row(tseg, ngroups, row0);
+  if (s >= comp_off[g + 1] - comp_off[g]) return;
+  const int mrow0 = (comp_off[g] + s) * D;  // first row of this matrix
+  const float* a = dc + (int64_t)s * Bp * D;
+
+  const TileAcc acc =
+      tile_mainloop_f32(a, Bp, mats, mrow0 + D, D, row0, mrow0 + bj * BN, lds,
+                        lds + BK * (BM + LDS_PAD));
+  tile_epilogue_quad(acc, a, D, row0, Bp, bj * BN, Bp, s * gridDim.x + bj,
+                     red_v, pquad);
+}
+
+// Folds the column-block partials of each (slot, padded row) in ascending bj
+// and writes the row's final score to its source row. mode 0: the quadratic
+// form of slot 0 (Mahalanobis). mode 1: -logsumexp_s(logc - q / 2) over the
+// group's slots (mixture NLL), with accurate expf / logf. A group without
+// components scores +inf; pad rows and rows at or past tseg[ngroups] write
+// nothing (`out` is pre-filled with +inf by the caller).
+constexpr int QUAD_MAX_SLOTS = 8;
+
+__global__ void grouped_gauss_final_kernel(
+    const float* __restrict__ pquad, const int* __restrict__ tseg,
+    const int* __restrict__ comp_off, int ngroups, int Bp, int jb,
+    const int* __restrict__ rowmap, int out_rows,
+    const float* __restrict__ logc,  // [J], mode 1 only
+    int mode, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Bp || i >= tseg[ngroups]) return;
+  const int src = rowmap[i];
+  if (src < 0 || src >= out_rows) return;
+  const int g = class_of_row(tseg, ngroups, i);
+  const int c0 = comp_off[g];
+  int ncomp = comp_off[g + 1] - c0;
+  if (ncomp > QUAD_MAX_SLOTS) ncomp = QUAD_MAX_SLOTS;
+  if (ncomp <= 0) {
+    out[src] = INFINITY;
+    return;
+  }
+  float t[QUAD_MAX_SLOTS];
+  float tmax = -INFINITY;
+#pragma unroll
+  for (int s = 0; s < QUAD_MAX_SLOTS; ++s) {
+    t[s] = -INFINITY;
+    if (s < ncomp) {
+      float q = 0.f;
+      for (int b = 0; b < jb; ++b) q += pquad[((int64_t)s * jb + b) * Bp + i];
+      t[s] = (mode == 0) ? q : (logc[c0 + s] - 0.5f * q);
+      tmax = fmaxf(tmax, t[s]);
+    }
+  }
+  if (mode == 0) {
+    out[src] = t[0];
+    return;
+  }
+  if (!(tmax > -INFINITY && tmax < INFINITY)) {
+    // every component underflowed to -inf (score +inf), or a NaN / +inf term
+    out[src] = (tmax == -INFINITY) ? INFINITY : -tmax;
+    return;
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int s = 0; s < QUAD_MAX_SLOTS; ++s)
+    if (s < ncomp) sum += expf(t[s] - tmax);
+  out[src] = -(tmax + logf(sum));
 }
 
 // ---------------------------------------------------------------------------
@@ -827,6 +967,26 @@ void launch_grouped_rowmin_plan(const short* a, int a_rows, const short* b,
   grouped_rowmin_final_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pval, pidx, tseg, nseg, nclasses, bp, rowmap, a_rows, btable, out_dsa,
       out_dist, out_idx);
+}
+
+// Sync-free path: quadratic forms of the centred workspace `dc` against the
+// groups' matrices, then the final Mahalanobis (logc == nullptr) or mixture
+// NLL scores per source row. `slots` is the largest component count.
+int grouped_gauss_max_slots() { return QUAD_MAX_SLOTS; }
+
+void launch_grouped_gauss_plan(const float* dc, const float* mats,
+                               const int* tseg, const int* comp_off,
+                               const int* rowmap, int out_rows,
+                               const float* logc, int ngroups, int bp, int d,
+                               int slots, float* pquad, float* out,
+                               hipStream_t s) {
+  const int jb = ceil_div(d, BN);
+  dim3 grid(jb, ceil_div(bp, BM), slots);
+  grouped_quad_kernel<<<grid, 256, 0, s>>>(dc, mats, tseg, comp_off, ngroups,
+                                           bp, d, pquad);
+  grouped_gauss_final_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
+      pquad, tseg, comp_off, ngroups, bp, jb, rowmap, out_rows, logc,
+      logc != nullptr ? 1 : 0, out);
 }
 
 // Sync-free path: `a` is the whitened workspace (already in padded layout),

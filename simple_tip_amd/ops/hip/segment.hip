@@ -250,7 +250,84 @@ __launch_bounds__(256) __global__ void grouped_whiten_bf16_kernel(
   }
 }
 
+// Grouped centring for the Gaussian scorers (pairwise.hip,
+// grouped_quad_kernel): for padded row p of group g and component slot s
+//   dc[s][p][:] = float(x[rowmap[p]][:]) - means[comp_off[g] + s][:]
+// and zeros for pad rows and for slots the group does not have, so the tile
+// main loop needs no gather and no mean. One wave per (slot, padded row);
+// rows at or past tseg[G] belong to no group and are never read, so they are
+// skipped. Memory-bound: 16-byte stores (and fp32 loads) where D % 4 == 0.
+// The difference is taken in fp32 on the (exact) widened input, which is the
+// value the oracle centres too.
+template <bool BF16>
+__launch_bounds__(256) __global__ void grouped_center_kernel(
+    const void* __restrict__ xv,       // [B, D] fp32 or bf16 source rows
+    int B, int D,
+    const int* __restrict__ rowmap,    // [Bp]
+    const int* __restrict__ tseg,      // [G+1]
+    const int* __restrict__ comp_off,  // [G+1]
+    int ngroups, int Bp,
+    const float* __restrict__ means,   // [J, D]
+    float* __restrict__ dc) {          // [S, Bp, D]
+  const int p = blockIdx.x * (blockDim.x / WAVE) + wave_id();
+  const int s = blockIdx.y;
+  if (p >= Bp || p >= tseg[ngroups]) return;
+  int g = 0;
+  for (int c = 0; c < ngroups; ++c)
+    if (tseg[c] <= p) g = c;
+  int src = rowmap[p];
+  if (src >= B) src = -1;
+  const bool live = src >= 0 && s < comp_off[g + 1] - comp_off[g];
+  float* o = dc + ((int64_t)s * Bp + p) * D;
+  const int lane = lane_id();
+  const float* mu = means + (int64_t)(live ? comp_off[g] + s : 0) * D;
+  const float* xf =
+      static_cast<const float*>(xv) + (int64_t)(live ? src : 0) * D;
+  const short* xh =
+      static_cast<const short*>(xv) + (int64_t)(live ? src : 0) * D;
+  if ((D & 3) == 0) {
+    for (int k4 = lane; k4 < D / 4; k4 += WAVE) {
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live) {
+        const float4 m = *reinterpret_cast<const float4*>(mu + k4 * 4);
+        float4 v;
+        if (BF16) {
+          const short4 h = *reinterpret_cast<const short4*>(xh + k4 * 4);
+          v = make_float4(bf16_bits_to_float(h.x), bf16_bits_to_float(h.y),
+                          bf16_bits_to_float(h.z), bf16_bits_to_float(h.w));
+        } else {
+          v = *reinterpret_cast<const float4*>(xf + k4 * 4);
+        }
+        r = make_float4(v.x - m.x, v.y - m.y, v.z - m.z, v.w - m.w);
+      }
+      *reinterpret_cast<float4*>(o + k4 * 4) = r;
+    }
+  } else {
+    for (int k = lane; k < D; k += WAVE) {
+      float r = 0.f;
+      if (live) r = (BF16 ? bf16_bits_to_float(xh[k]) : xf[k]) - mu[k];
+      o[k] = r;
+    }
+  }
+}
+
 // ---- host-side launchers (called from bindings.cpp) ----
+
+void launch_grouped_center(const void* x, bool bf16, int b, int d,
+                           const int* rowmap, const int* tseg,
+                           const int* comp_off, int ngroups, int bp,
+                           const float* means, int slots, float* dc,
+                           hipStream_t s) {
+  const int wpb = 4;
+  dim3 grid(ceil_div(bp, wpb), slots);
+  if (bf16) {
+    grouped_center_kernel<true><<<grid, wpb * WAVE, 0, s>>>(
+        x, b, d, rowmap, tseg, comp_off, ngroups, bp, means, dc);
+  } else {
+    grouped_center_kernel<false><<<grid, wpb * WAVE, 0, s>>>(
+        x, b, d, rowmap, tseg, comp_off, ngroups, bp, means, dc);
+  }
+}
 
 int segment_plan_max_classes() { return PLAN_MAX_C; }
 

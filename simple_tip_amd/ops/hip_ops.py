@@ -174,6 +174,124 @@ def mc_dropout_stats(
     return votes, mean_probs, mean_entropy
 
 
+#: Cap on the centred workspace of one grouped-Gaussian launch, in bytes
+#: (``slots * padded_rows * D * 4``). A batch whose workspace would be larger
+#: is scored in row chunks; per-row results do not depend on the batch a row
+#: arrives in, so chunking is invisible in the output. 256 MiB holds both
+#: measured shapes in one chunk (serving batch 20480 x 64; study batch
+#: 10000 x 1600 with three components, which fits up to 12672 rows) and
+#: stays far below the HBM a fitted study already occupies. A chunk is never
+#: smaller than one 128-row block, so a tiny cap (tests set one) only means
+#: many chunks.
+GAUSS_WORKSPACE_BYTES = 256 << 20
+
+
+class GaussianTables:
+    """Validated, device-resident tables of a grouped Gaussian scorer.
+
+    Built once per fit (the validation reads ``comp_off`` on the host); every
+    call through :func:`grouped_gaussian_scores_tables` is then free of host
+    copies. ``means`` [J, D], ``mats`` [J, D, D] and ``logc`` [J] are fp32,
+    ``comp_off`` int32 [G+1].
+    """
+
+    def __init__(self, comp_off, means, mats, logc, device):
+        from . import fallback
+
+        if mats.dtype != torch.float32:
+            raise ValueError("mats must be float32 on the GPU path")
+        self.G, self.J, self.D, self.slots = fallback.gaussian_check_envelope(
+            comp_off, means, mats, logc
+        )
+        self.device = torch.device(device)
+        f32 = dict(device=self.device, dtype=torch.float32)
+        self.comp_off = torch.as_tensor(comp_off).to(self.device, torch.int32).contiguous()
+        self.means = means.to(**f32).contiguous()
+        self.mats = mats.to(**f32).contiguous()
+        self.logc = None if logc is None else logc.to(**f32).contiguous()
+        self.jb = (self.D + 127) // 128
+        self._ws = {}
+
+    def chunk_rows(self) -> int:
+        """Largest 128-multiple batch whose workspace fits the cap."""
+        per_row = max(self.slots, 1) * self.D * 4
+        rows = GAUSS_WORKSPACE_BYTES // per_row - 128 * self.G
+        return max(128, rows // 128 * 128)
+
+    def workspace(self, b: int, own_plan: bool):
+        """Per-batch-size scratch, reused from call to call on one stream."""
+        ws = self._ws.get(b)
+        if ws is None:
+            if len(self._ws) >= 4:
+                self._ws.clear()
+            bp = _ext.segment_plan_rows(b, self.G)
+            slots = max(self.slots, 1)
+            f32 = dict(device=self.device, dtype=torch.float32)
+            ws = {
+                "dc": torch.empty(slots * bp * self.D, **f32),
+                "pquad": torch.empty(slots * self.jb * bp, **f32),
+            }
+            self._ws[b] = ws
+        if own_plan and "tseg" not in ws:
+            bp = _ext.segment_plan_rows(b, self.G)
+            i32 = dict(device=self.device, dtype=torch.int32)
+            ws["tseg"] = torch.empty(self.G + 1, **i32)
+            ws["rowmap"] = torch.empty(bp, **i32)
+            ws["dest"] = torch.empty(b, **i32)
+        return ws
+
+
+def grouped_gaussian_into(x, tables: GaussianTables, tseg, rowmap, out) -> None:
+    """Score ``x`` [B, D] (fp32 or bf16) through an existing segment plan over
+    ``tables.G`` groups into ``out`` [B] (fp32, pre-filled with +inf)."""
+    ws = tables.workspace(x.shape[0], own_plan=False)
+    _ext.grouped_gauss_plan(
+        x, tseg, rowmap, tables.comp_off, tables.means, tables.mats,
+        tables.logc, max(tables.slots, 1), ws["dc"], ws["pquad"], out,
+    )
+
+
+def grouped_gaussian_scores_tables(
+    x: torch.Tensor, group: torch.Tensor, tables: GaussianTables, out=None
+) -> torch.Tensor:
+    """float32 [N] scores; no host copy, one plan + three kernels per chunk.
+    ``out`` (optional) is a float32 [N] tensor already filled with +inf."""
+    if x.dim() != 2 or x.shape[1] != tables.D:
+        raise ValueError(f"x must be [N, {tables.D}]")
+    if x.dtype != torch.bfloat16:
+        x = x.float()
+    x = x.contiguous()
+    group = group.to(x.device, torch.int64).contiguous()
+    n = x.shape[0]
+    if out is None:
+        out = torch.full((n,), float("inf"), dtype=torch.float32, device=x.device)
+    if n == 0 or tables.slots == 0:
+        return out
+    step = tables.chunk_rows()
+    for lo in range(0, n, step):
+        hi = min(n, lo + step)
+        ws = tables.workspace(hi - lo, own_plan=True)
+        _ext.segment_plan_out(
+            group[lo:hi], tables.G, ws["tseg"], ws["rowmap"], ws["dest"]
+        )
+        grouped_gaussian_into(
+            x[lo:hi], tables, ws["tseg"], ws["rowmap"], out[lo:hi]
+        )
+    return out
+
+
+def grouped_gaussian_scores(
+    x: torch.Tensor,
+    group: torch.Tensor,
+    comp_off: torch.Tensor,
+    means: torch.Tensor,
+    mats: torch.Tensor,
+    logc: torch.Tensor = None,
+) -> torch.Tensor:
+    tables = GaussianTables(comp_off, means, mats, logc, x.device)
+    return grouped_gaussian_scores_tables(x, group, tables)
+
+
 def _empty(t):
     return torch.empty(0, dtype=torch.float32, device=t.device)
 
