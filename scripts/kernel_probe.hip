@@ -3,6 +3,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I simple_tip_amd/ops/hip \
 //          scripts/kernel_probe.hip -o gpurun_out/kernel_probe
 // Run:   ./kernel_probe pairwise|resblock [iters]
+//        ./kernel_probe grouped16 [iters test/cls train/cls k [generic]]
 //
 // Includes the production kernel sources directly so the profiled code is
 // byte-identical to what the extension ships.
@@ -344,8 +345,11 @@ static void run_verify(int perclass_test, int perclass_train, int k) {
 }
 
 // bf16 grouped rowmin at the same geometry (cross-checks vs fp32 run).
+// `generic` forces grouped_pairwise_bf16_kernel where the pipelined kernel
+// would serve, so one binary times both on the same operands.
 static void run_grouped_bf16(int iters, int perclass_test, int perclass_train,
-                             int k) {
+                             int k, bool generic) {
+  rowmin_bf16_force_generic(generic);
   const int C = 10;
   const int pc_pad = (perclass_test + 127) / 128 * 128;
   const int bp = C * pc_pad;
@@ -416,9 +420,10 @@ static void run_grouped_bf16(int iters, int perclass_test, int perclass_train,
     dsum += dh[i];
     isum += ih[i];
   }
-  printf("grouped_rowmin_bf16 C=%d bp=%d ntr/cls=%d k=%d: %.3f ms/iter, "
+  printf("grouped_rowmin_bf16[%s] C=%d bp=%d ntr/cls=%d k=%d: %.3f ms/iter, "
          "%.1f TF  checksum d=%.6e i=%lld\n",
-         C, bp, perclass_train, k, ms / iters, tf, dsum, isum);
+         rowmin_bf16_pipelined_launches() ? "pipelined" : "generic", C, bp,
+         perclass_train, k, ms / iters, tf, dsum, isum);
 }
 
 static void run_downblock(int iters, int variant) {
@@ -472,7 +477,8 @@ int main(int argc, char** argv) {
   else if (!strcmp(which, "grouped16"))
     run_grouped_bf16(iters, argc > 3 ? atoi(argv[3]) : 1024,
                      argc > 4 ? atoi(argv[4]) : 1500,
-                     argc > 5 ? atoi(argv[5]) : 4096);
+                     argc > 5 ? atoi(argv[5]) : 4096,
+                     argc > 6 && !strcmp(argv[6], "generic"));
   else if (!strcmp(which, "verify"))
     run_verify(argc > 2 ? atoi(argv[2]) : 1024, argc > 3 ? atoi(argv[3]) : 1500,
                argc > 4 ? atoi(argv[4]) : 4096);

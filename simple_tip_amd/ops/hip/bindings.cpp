@@ -35,6 +35,12 @@ void launch_grouped_rowmin_bf16(const short*, const short*, const float*,
 void launch_grouped_kde_bf16(const short*, const short*, const float*,
                              const float*, const int*, const int*, int, int,
                              int, int, float2*, float*, hipStream_t);
+// bf16 row-min dispatch (pairwise.hip): force the generic kernel, count the
+// launches that took the pipelined one, and the pipelined kernel's geometry
+void rowmin_bf16_force_generic(bool);
+int64_t rowmin_bf16_pipelined_launches();
+int rowmin_bf16_pipeline_bk();
+int rowmin_bf16_pipeline_nbuf();
 void launch_profile(int, const float*, const unsigned char*, const float*,
                     const float*, float, int, int, int, int,
                     unsigned long long*, long long*, hipStream_t);
@@ -874,6 +880,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_kde", &grouped_kde);
   m.def("grouped_rowmin_bf16", &grouped_rowmin_bf16);
   m.def("grouped_kde_bf16", &grouped_kde_bf16);
+  m.def("rowmin_bf16_force_generic", &rowmin_bf16_force_generic);
+  m.def("rowmin_bf16_pipelined_launches", &rowmin_bf16_pipelined_launches);
+  m.def("rowmin_bf16_pipeline_bk", &rowmin_bf16_pipeline_bk);
+  m.def("rowmin_bf16_pipeline_nbuf", &rowmin_bf16_pipeline_nbuf);
   m.def("segment_plan", &segment_plan);
   m.def("segment_plan_out", &segment_plan_out);
   m.def("segment_plan_rows", &segment_plan_rows);

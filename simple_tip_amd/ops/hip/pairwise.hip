@@ -498,10 +498,14 @@ __global__ void grouped_gauss_final_kernel(
 // measured ~95-119 TF; dense bf16 peak is ~2.5 PF). Fragment layout is the
 // one hardware-verified by mfma_probe (resnet_fused.hip): A lane l holds
 // A[i=l&15][k=(l>>4)*8+e]; B lane l holds B-col[j=l&15][same k]; D row =
-// (l>>4)*4+reg, col = l&15. LDS tiles are [128][BBK+8] halves — the +8 pad
-// makes the 16-lane fragment gathers stride 5 units (coprime to the bank
-// period). Partial outputs are identical in format to the fp32 grouped
-// kernel, so the same combine kernels run afterwards.
+// (l>>4)*4+reg, col = l&15. LDS tiles are [128][BROW] halves. ds_read_b128
+// is served in four groups of 16 lanes that are NOT contiguous ({0-3, 12-15,
+// 20-27}, ...), so a group spans two fg values: the 5-unit row stride of
+// BROW = 40 is coprime to the 16-unit bank row only within one fg, and the
+// fragment reads are 2-way conflicted (as at 56 and 72; 48 models
+// conflict-free). The pipelined kernel below uses unpadded 128-B rows with
+// an XOR swizzle instead. Partial outputs are identical in format to the
+// fp32 grouped kernel, so the same combine kernels run afterwards.
 // ---------------------------------------------------------------------------
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
@@ -510,7 +514,8 @@ using f32x4b = __attribute__((ext_vector_type(4))) float;
 constexpr int BBK = 32;             // k per MFMA / staging step
 // LDS halves per tile row. Must be a multiple of 8 (16-B-aligned b128
 // reads); the pad past BBK sets the bank-group stride of the fragment
-// gathers. TIP_BROW is sweepable on hardware (40 = 5-unit stride default).
+// gathers. TIP_BROW is sweepable on hardware (40 = 5-unit stride default;
+// profiles/r10_rowmin_pipeline.md has the sweep against 48).
 #ifndef TIP_BROW
 #define TIP_BROW 40
 #endif
@@ -558,6 +563,18 @@ TIP_DEV void bstage_write(short* lds, const BStage& s) {
   *reinterpret_cast<bf16x8*>(&lds[r * BROW + kq]) = s.v[0];
   *reinterpret_cast<bf16x8*>(&lds[r * BROW + kq + 8]) = s.v[1];
 }
+
+// Per-row epilogue of the bf16 block tile at (row0, col0), shared by the
+// generic and the pipelined kernel. red_* must not alias LDS that another
+// wave may still be reading when this is called.
+template <int EPI, bool GATHER>
+TIP_DEV void bf16_tile_epilogue(
+    const f32x4b (&acc)[4][4], const float* __restrict__ anorm,
+    const float* __restrict__ bnorm, const int* __restrict__ rowmap,
+    int a_rows, int row0, int col0, int ncol1, int Bp, int bj,
+    float (*red_v)[2], int (*red_i)[2], float (*red_s)[2],
+    float* __restrict__ pmin_val, int* __restrict__ pmin_idx,
+    float2* __restrict__ pkde);
 
 // GATHER: A is the UNPADDED source [a_rows, K] and padded row p reads source
 // row rowmap[p] (zeros where it is -1), its norm through the same index, so
@@ -641,6 +658,25 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
     __syncthreads();
   }
 
+  bf16_tile_epilogue<EPI, GATHER>(acc, anorm, bnorm, rowmap, a_rows, row0,
+                                  col0, ncol1, Bp, bj, red_v, red_i, red_s,
+                                  pmin_val, pmin_idx, pkde);
+}
+
+template <int EPI, bool GATHER>
+TIP_DEV void bf16_tile_epilogue(
+    const f32x4b (&acc)[4][4], const float* __restrict__ anorm,
+    const float* __restrict__ bnorm, const int* __restrict__ rowmap,
+    int a_rows, int row0, int col0, int ncol1, int Bp, int bj,
+    float (*red_v)[2], int (*red_i)[2], float (*red_s)[2],
+    float* __restrict__ pmin_val, int* __restrict__ pmin_idx,
+    float2* __restrict__ pkde) {
+  const int lane = lane_id();
+  const int wr = wave_id() >> 1;
+  const int wc = wave_id() & 1;
+  const int fj = lane & 15;
+  const int fg = lane >> 4;
+
   // Epilogue. D tile (tr, tc): row i = wr*64 + tr*16 + fg*4 + reg,
   // col j = wc*64 + tc*16 + fj. Per row: reduce over this wave's 64 cols
   // (4 tc in registers + 16 fj lanes via xor shuffles), stash per col-half.
@@ -704,6 +740,167 @@ __launch_bounds__(256, 2) __global__ void grouped_pairwise_bf16_kernel(
   __syncthreads();
   merge_halves_store<EPI>(red_v, red_i, red_s, row0, Bp, Bp, bj, pmin_val,
                           pmin_idx, pkde);
+}
+
+// ---------------------------------------------------------------------------
+// Pipelined bf16 grouped row-min (docs/kernels.md "Pipelined row-min"). Same
+// tile, waves, MFMA and epilogue as grouped_pairwise_bf16_kernel<EPI_ROWMIN>,
+// and every accumulator is the same chain over k ascending in steps of 32, so
+// the partials are the same bits. What differs is the staging: K-tiles of
+// PBK = 64 go global -> LDS by 16-byte direct-to-LDS loads into PNBUF = 2
+// buffers, tile t+1 issued before tile t's fragment reads, one barrier per
+// tile. Serves K % PBK == 0 and 16-byte-aligned operands only; the
+// launchers dispatch.
+//
+// LDS image of one operand tile: [128 rows][8 units of 16 B], lane-linear as
+// the DMA writes it (thread t, pass q: row q*32 + t/8, unit t%8). Unit u of
+// row r holds k-unit u ^ (r & 7): the XOR is applied to the per-lane SOURCE
+// address and again on the fragment read, which makes every ds_read_b128
+// lane group hit 16 distinct 16-B slots of the 256-B bank row.
+//
+// Tile t (buffer t & 1) is staged in iteration t-1 after the barrier, retired
+// by the vmcnt(0) every wave executes before iteration t's barrier, read only
+// after that barrier, and restaged in iteration t+1 after the next one. At
+// most one tile is in flight and none crosses a barrier un-waited, so plain
+// __syncthreads() is enough (full accounting: docs/kernels.md).
+// ---------------------------------------------------------------------------
+
+constexpr int PBK = 64;              // k per staged tile: two MFMA k-steps
+constexpr int PNBUF = 2;             // LDS buffers per operand
+constexpr int PTILE = 128 * PBK;     // halves per operand tile (16 KiB)
+
+// Source of all-zero units for pad rows: the DMA of such a lane reads here
+// (and does not advance with k) instead of being branched around.
+static __device__ __attribute__((aligned(128))) short g_zero_units[PBK];
+
+// Block order of the pipelined kernel: 1 deals contiguous runs of the
+// (column block fast, row block slow) order to the blocks that share an XCD
+// (T1, bijective), so that a row panel's column blocks meet in one L2; 0
+// keeps (blockIdx.x, blockIdx.y) as they come, which deals them across all
+// eight. 1 measured 6 - 7 % faster (profiles/r10_rowmin_pipeline.md).
+#ifndef TIP_ROWMIN_XCD
+#define TIP_ROWMIN_XCD 1
+#endif
+
+using lds_ptr_t = __attribute__((address_space(3))) void*;
+using glb_ptr_t = const __attribute__((address_space(1))) void*;
+
+template <bool GATHER>
+__launch_bounds__(256, 2) __global__ void grouped_rowmin_bf16_pipe_kernel(
+    const short* __restrict__ A,      // [Bp, K] bf16 (GATHER: [a_rows, K])
+    const short* __restrict__ B,      // [Ntot, K] bf16 class-concatenated
+    const float* __restrict__ anorm, const float* __restrict__ bnorm,
+    const int* __restrict__ tseg, const int* __restrict__ nseg,
+    const int* __restrict__ rowmap,   // GATHER: [Bp] padded row -> A row
+    int a_rows,                       // GATHER: rows of A
+    int nclasses, int Bp, int K,
+    float* __restrict__ pmin_val, int* __restrict__ pmin_idx) {
+  // one array: staging ring [PNBUF][A, B][128][PBK]; its head is reused as
+  // red_v / red_i after the loop
+  __shared__ __attribute__((aligned(16))) short lds[PNBUF * 2 * PTILE];
+
+  int bi = blockIdx.y, bj = blockIdx.x;
+  if (TIP_ROWMIN_XCD) {
+    const int nwg = gridDim.x * gridDim.y;
+    const int id = blockIdx.y * gridDim.x + blockIdx.x;
+    const int q = nwg / 8, r = nwg % 8;
+    const int xcd = id % 8, pos = id / 8;
+    const int newid =
+        (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+    bi = newid / gridDim.x;
+    bj = newid % gridDim.x;
+  }
+  const int row0 = bi * BM;
+  if (row0 >= tseg[nclasses]) return;
+  const int cls = class_of_row(tseg, nclasses, row0);
+  const int ncol0 = nseg[cls], ncol1 = nseg[cls + 1];
+  const int col0 = ncol0 + bj * BN;
+  if (col0 >= ncol1) return;
+
+  const int t = threadIdx.x;
+  const int lane = lane_id();
+  const int wid = wave_id();
+  const int wr = wid >> 1;
+  const int wc = wid & 1;
+  const int fj = lane & 15;
+  const int fg = lane >> 4;
+
+  // Staging sources: pass q of this thread fills row q*32 + t/8, unit t%8,
+  // from k-unit (t%8) ^ (row & 7); a pad row reads g_zero_units, step 0.
+  const int sunit = (t & 7) ^ ((t >> 3) & 7);
+  const short* asrc[4];
+  const short* bsrc[4];
+  int astep[4], bstep[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = q * 32 + (t >> 3);
+    int arow = row0 + r;
+    bool aok = arow < Bp;
+    if (GATHER) {
+      arow = aok ? rowmap[arow] : -1;
+      aok = arow >= 0 && arow < a_rows;
+    }
+    asrc[q] = (aok ? A + (int64_t)arow * K : g_zero_units) + sunit * 8;
+    astep[q] = aok ? PBK : 0;
+    const int brow = col0 + r;
+    const bool bok = brow < ncol1;
+    bsrc[q] = (bok ? B + (int64_t)brow * K : g_zero_units) + sunit * 8;
+    bstep[q] = bok ? PBK : 0;
+  }
+  // wave-uniform LDS destination of pass q: the hardware adds lane * 16 B
+  auto stage = [&](int buf) {
+    short* dst = lds + buf * 2 * PTILE + wid * 64 * 8;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      __builtin_amdgcn_global_load_lds((glb_ptr_t)asrc[q],
+                                       (lds_ptr_t)(dst + q * 256 * 8), 16, 0,
+                                       0);
+      __builtin_amdgcn_global_load_lds(
+          (glb_ptr_t)bsrc[q], (lds_ptr_t)(dst + PTILE + q * 256 * 8), 16, 0, 0);
+      asrc[q] += astep[q];
+      bsrc[q] += bstep[q];
+    }
+  };
+
+  // fragment read offsets (halves) inside an operand tile: row wX*64 + fj
+  // (+ 16 rows per fragment), k-step s at unit (s*4 + fg) ^ (fj & 7)
+  const int aoff = (wr * 64 + fj) * PBK;
+  const int boff = PTILE + (wc * 64 + fj) * PBK;
+  const int uoff[2] = {((fg) ^ (fj & 7)) * 8, ((4 + fg) ^ (fj & 7)) * 8};
+
+  f32x4b acc[4][4] = {};
+  const int ntiles = K / PBK;
+  stage(0);
+  for (int kt = 0; kt < ntiles; ++kt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (kt + 1 < ntiles) stage((kt + 1) & 1);
+    const short* cur = lds + (kt & 1) * 2 * PTILE;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bf16x8 af[4], bf[4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        af[f] = *reinterpret_cast<const bf16x8*>(
+            &cur[aoff + f * 16 * PBK + uoff[s]]);
+        bf[f] = *reinterpret_cast<const bf16x8*>(
+            &cur[boff + f * 16 * PBK + uoff[s]]);
+      }
+#pragma unroll
+      for (int tr = 0; tr < 4; ++tr)
+#pragma unroll
+        for (int tc = 0; tc < 4; ++tc)
+          acc[tr][tc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              af[tr], bf[tc], acc[tr][tc], 0, 0, 0);
+    }
+  }
+
+  __syncthreads();  // every wave is done reading before red_* reuse the ring
+  float(*red_v)[2] = reinterpret_cast<float(*)[2]>(lds);
+  int(*red_i)[2] = reinterpret_cast<int(*)[2]>(lds + BM * 2 * 2);
+  bf16_tile_epilogue<EPI_ROWMIN, GATHER>(
+      acc, anorm, bnorm, rowmap, a_rows, row0, col0, ncol1, Bp, bj, red_v,
+      red_i, nullptr, pmin_val, pmin_idx, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -924,6 +1121,27 @@ void launch_grouped_kde(const float* a, const float* b, const float* an,
       pkde, tseg, nseg, nclasses, bp, out_lse);
 }
 
+// Dispatch of the bf16 row-min launchers. The pipelined kernel serves K a
+// positive multiple of its K-tile and 16-byte-aligned operands (rows are then
+// 16-byte aligned too); everything else, and everything while the generic
+// kernel is forced, runs grouped_pairwise_bf16_kernel. The counter tells
+// tests which kernel a call took.
+static bool g_rowmin_force_generic = false;
+static int64_t g_rowmin_pipelined_launches = 0;
+
+void rowmin_bf16_force_generic(bool on) { g_rowmin_force_generic = on; }
+int64_t rowmin_bf16_pipelined_launches() { return g_rowmin_pipelined_launches; }
+int rowmin_bf16_pipeline_bk() { return PBK; }
+int rowmin_bf16_pipeline_nbuf() { return PNBUF; }
+
+static bool rowmin_bf16_use_pipeline(const short* a, const short* b, int k) {
+  const bool ok = !g_rowmin_force_generic && k > 0 && k % PBK == 0 &&
+                  ((reinterpret_cast<uintptr_t>(a) |
+                    reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+  if (ok) ++g_rowmin_pipelined_launches;
+  return ok;
+}
+
 void launch_grouped_rowmin_bf16(const short* a, const short* b,
                                 const float* an, const float* bn,
                                 const int* tseg, const int* nseg,
@@ -931,9 +1149,13 @@ void launch_grouped_rowmin_bf16(const short* a, const short* b,
                                 float* pval, int* pidx, float* out_dist,
                                 int64_t* out_idx, hipStream_t s) {
   dim3 grid(jb_max, ceil_div(bp, BM));
-  grouped_pairwise_bf16_kernel<EPI_ROWMIN, false><<<grid, 256, 0, s>>>(
-      a, b, an, bn, tseg, nseg, nullptr, 0, nclasses, bp, k, pval, pidx,
-      nullptr);
+  if (rowmin_bf16_use_pipeline(a, b, k))
+    grouped_rowmin_bf16_pipe_kernel<false><<<grid, 256, 0, s>>>(
+        a, b, an, bn, tseg, nseg, nullptr, 0, nclasses, bp, k, pval, pidx);
+  else
+    grouped_pairwise_bf16_kernel<EPI_ROWMIN, false><<<grid, 256, 0, s>>>(
+        a, b, an, bn, tseg, nseg, nullptr, 0, nclasses, bp, k, pval, pidx,
+        nullptr);
   grouped_rowmin_combine_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pval, pidx, tseg, nseg, nclasses, bp, out_dist, out_idx);
 }
@@ -961,9 +1183,13 @@ void launch_grouped_rowmin_plan(const short* a, int a_rows, const short* b,
                                 float* pval, int* pidx, float* out_dsa,
                                 float* out_dist, int* out_idx, hipStream_t s) {
   dim3 grid(jb_max, ceil_div(bp, BM));
-  grouped_pairwise_bf16_kernel<EPI_ROWMIN, true><<<grid, 256, 0, s>>>(
-      a, b, an, bn, tseg, nseg, rowmap, a_rows, nclasses, bp, k, pval, pidx,
-      nullptr);
+  if (rowmin_bf16_use_pipeline(a, b, k))
+    grouped_rowmin_bf16_pipe_kernel<true><<<grid, 256, 0, s>>>(
+        a, b, an, bn, tseg, nseg, rowmap, a_rows, nclasses, bp, k, pval, pidx);
+  else
+    grouped_pairwise_bf16_kernel<EPI_ROWMIN, true><<<grid, 256, 0, s>>>(
+        a, b, an, bn, tseg, nseg, rowmap, a_rows, nclasses, bp, k, pval, pidx,
+        nullptr);
   grouped_rowmin_final_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pval, pidx, tseg, nseg, nclasses, bp, rowmap, a_rows, btable, out_dsa,
       out_dist, out_idx);
