@@ -32,6 +32,7 @@ setup(
                 os.path.join(HIP_DIR, "resnet_stages.hip"),
                 os.path.join(HIP_DIR, "scores.hip"),
                 os.path.join(HIP_DIR, "mcdropout.hip"),
+                os.path.join(HIP_DIR, "mctail.hip"),
             ],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],

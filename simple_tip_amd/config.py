@@ -34,8 +34,11 @@ DROPOUT_SAMPLE_SIZE = 200
 
 #: How BaseModel computes the MC-dropout variation ratio when it is not told:
 #: "replay" (re-run the whole model per sample), "fused" (trunk once + the
-#: mc_dropout_votes kernel; Dropout->Linear heads only) or "auto" (fused
-#: where applicable, else replay). Override with TIP_VR_MODE.
+#: mc_dropout_votes kernel for Dropout->Linear heads; embedding + attention
+#: once + the mc_transformer_votes kernel for a model with a dropout_tail(),
+#: i.e. the IMDB transformer) or "auto" (the fused head where applicable,
+#: else replay). "auto" never picks the transformer tail: that path is an
+#: explicit "fused" opt-in. Override with TIP_VR_MODE.
 VR_MODES = ("replay", "fused", "auto")
 
 

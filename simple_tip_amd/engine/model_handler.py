@@ -10,7 +10,11 @@ MI355X-native differences:
   with device RNG and on-device vote counting ("replay", the default), or,
   for models that end in Dropout -> Linear, runs the deterministic trunk once
   and all masked heads in one kernel (``vr_mode="fused"``,
-  ops.mc_dropout_votes: seeded, batch- and shard-invariant);
+  ops.mc_dropout_votes: seeded, batch- and shard-invariant); a model with
+  a ``dropout_tail()`` (the IMDB transformer: four dropouts behind a
+  deterministic attention prefix) runs embedding + attention once and all
+  masked tails in one kernel (ops.mc_transformer_votes), on an explicit
+  ``vr_mode="fused"`` only;
 - the other sampling quantifiers (predictive entropy, mutual information,
   mean softmax) are opt-in (``mc_quantifiers``) and come from the same
   samples: on the fused path one ops.mc_dropout_stats call per batch
@@ -30,7 +34,7 @@ from ..config import DROPOUT_SAMPLE_SIZE
 from ..core.quantifiers import probs_entropy, mc_sample_scores
 from ..core.timer import DeviceTimer
 from .. import ops
-from ..models.base import TapModel
+from ..models.base import DropoutTail, TapModel
 
 logger = logging.getLogger(__name__)
 
@@ -57,10 +61,12 @@ class BaseModel:
         mc_quantifiers: Optional[Sequence[str]] = None,
     ):
         """``vr_mode`` selects how the variation ratio is sampled: "replay"
-        (whole model per sample), "fused" (trunk once + mc_dropout_votes;
-        ValueError unless the model ends in Dropout -> Linear within the
-        kernel envelope), "auto" (fused where applicable, else replay) or
-        None (``config.VR_MODE``). ``vr_seed`` seeds the fused masks.
+        (whole model per sample), "fused" (trunk once + mc_dropout_votes for
+        a model that ends in Dropout -> Linear, prefix once +
+        mc_transformer_votes for one with a ``dropout_tail()``; ValueError
+        for any other model or outside the kernel envelope), "auto" (the
+        fused head where applicable, else replay; never the tail) or None
+        (``config.VR_MODE``). ``vr_seed`` seeds the fused masks.
         ``mc_quantifiers`` names the sampling scores to return, out of "VR",
         "PE" (predictive entropy), "MI" (mutual information) and "MS"
         (negated max of the mean softmax); None means
@@ -214,22 +220,38 @@ class BaseModel:
             )
         return pred, uncertainties, times
 
-    def _fused_vr_head(self) -> Optional[Tuple[int, float, nn.Linear]]:
-        """The Dropout -> Linear head to fuse, or None for the replay path.
+    def _fused_vr_head(self):
+        """The Dropout -> Linear head ``(k, p, linear)`` or, in "fused" mode
+        only, the :class:`DropoutTail` to fuse; None for the replay path.
 
-        Raises ValueError in "fused" mode when the model has no such head or
-        the head is outside the kernel envelope on this device."""
+        Raises ValueError in "fused" mode when the model has neither or the
+        one it has is outside the kernel envelope on this device."""
         if self.vr_mode == "replay":
             return None
         head = self.model.dropout_head()
         if head is None:
-            if self.vr_mode == "fused":
+            if self.vr_mode != "fused":
+                return None
+            tail = self.model.dropout_tail()
+            if tail is None:
                 raise ValueError(
                     'vr_mode="fused" needs a model whose only Dropout feeds '
-                    "the final Linear layer (TapModel.dropout_head() is None "
+                    "the final Linear layer, or one with a dropout tail "
+                    "(TapModel.dropout_head() and dropout_tail() are None "
                     f"for {type(self.model).__name__})"
                 )
-            return None
+            q = tail.params
+            dims = (
+                q.w1.shape[1], self.model.input_shape[0], q.w1.shape[0],
+                q.w3.shape[0], q.w4.shape[0],
+            )
+            if not ops.mc_transformer_supported(q.w1, *dims):
+                raise ValueError(
+                    'vr_mode="fused": the transformer tail (E, T, F, H, C) = '
+                    f"{dims} is outside the mc_transformer_votes kernel "
+                    "envelope (E == 32, T <= 128, F <= 64, H <= 64, C <= 4)"
+                )
+            return tail
         lin = head[2]
         if not ops.mc_dropout_supported(
             lin.weight, lin.out_features, lin.in_features
@@ -277,12 +299,82 @@ class BaseModel:
         scores, times = self._sample_fused(x, head, row_base, extras=False)
         return scores["VR"], times
 
+    def _fused_scores(self, parts, prob_parts, ent_parts, num_classes, extras):
+        """VR (and the extras) from the per-batch votes / statistics."""
+        if not parts:
+            parts.append(torch.zeros(
+                0, num_classes, dtype=torch.int32, device=self.device
+            ))
+            prob_parts.append(torch.zeros(0, num_classes, device=self.device))
+            ent_parts.append(torch.zeros(0, device=self.device))
+        counts = torch.cat(parts, dim=0)
+        top = counts.max(dim=1).values.float()
+        vr = 1.0 - top / float(DROPOUT_SAMPLE_SIZE)
+        scores = {"VR": vr.cpu().numpy()}
+        if extras:
+            scores.update(self._extra_scores(
+                torch.cat(prob_parts, dim=0), torch.cat(ent_parts, dim=0)
+            ))
+        return scores
+
+    @torch.no_grad()
+    def _sample_tail(
+        self, x, tail: DropoutTail, row_base: int, extras: bool
+    ) -> Tuple[Dict[str, np.ndarray], List[float]]:
+        """Fused sampling of a transformer tail: embedding + attention once
+        per batch in fp32 (outside autocast, so the tail's inputs do not
+        depend on it), then ops.mc_transformer_votes or, with ``extras``,
+        ops.mc_transformer_stats (its votes are the same votes)."""
+        sampling_timer = DeviceTimer()
+        quant_timer = DeviceTimer()
+        self.model.eval()
+        tail_op = ops.mc_transformer_stats if extras else ops.mc_transformer_votes
+        params = ops.McTransformerParams(*[
+            v if name == "eps" else v.detach().float().contiguous()
+            for name, v in zip(tail.params._fields, tail.params)
+        ])
+        parts: List[torch.Tensor] = []
+        prob_parts: List[torch.Tensor] = []
+        ent_parts: List[torch.Tensor] = []
+        with sampling_timer:
+            for s0 in range(0, x.shape[0], self.predict_batch):
+                tokens = self._to_device(x[s0 : s0 + self.predict_batch])
+                with torch.autocast(self.device.type, enabled=False):
+                    emb = tail.embed(tokens).float()
+                    attn = tail.att(emb, emb, emb, need_weights=False)[0]
+                out = tail_op(
+                    emb.contiguous(),
+                    attn.float().contiguous(),
+                    params,
+                    tail.rates,
+                    DROPOUT_SAMPLE_SIZE,
+                    self.vr_seed,
+                    row_offset=int(row_base) + s0,
+                )
+                if extras:
+                    parts.append(out[0])
+                    prob_parts.append(out[1])
+                    ent_parts.append(out[2])
+                else:
+                    parts.append(out)
+        with quant_timer:
+            scores = self._fused_scores(
+                parts, prob_parts, ent_parts, params.w4.shape[0], extras
+            )
+        return (
+            scores,
+            [0.0, sampling_timer.get(), quant_timer.get(), 0.0],
+        )
+
     @torch.no_grad()
     def _sample_fused(
         self, x, head, row_base: int, extras: bool
     ) -> Tuple[Dict[str, np.ndarray], List[float]]:
         """Fused sampling: ops.mc_dropout_votes per batch, or, with
-        ``extras``, ops.mc_dropout_stats (its votes are the same votes)."""
+        ``extras``, ops.mc_dropout_stats (its votes are the same votes). A
+        :class:`DropoutTail` goes to :meth:`_sample_tail`."""
+        if isinstance(head, DropoutTail):
+            return self._sample_tail(x, head, row_base, extras)
         k, p, lin = head
         sampling_timer = DeviceTimer()
         quant_timer = DeviceTimer()
@@ -318,22 +410,9 @@ class BaseModel:
                 else:
                     parts.append(out)
         with quant_timer:
-            if not parts:
-                parts.append(torch.zeros(
-                    0, lin.out_features, dtype=torch.int32, device=self.device
-                ))
-                prob_parts.append(torch.zeros(
-                    0, lin.out_features, device=self.device
-                ))
-                ent_parts.append(torch.zeros(0, device=self.device))
-            counts = torch.cat(parts, dim=0)
-            top = counts.max(dim=1).values.float()
-            vr = 1.0 - top / float(DROPOUT_SAMPLE_SIZE)
-            scores = {"VR": vr.cpu().numpy()}
-            if extras:
-                scores.update(self._extra_scores(
-                    torch.cat(prob_parts, dim=0), torch.cat(ent_parts, dim=0)
-                ))
+            scores = self._fused_scores(
+                parts, prob_parts, ent_parts, lin.out_features, extras
+            )
         return (
             scores,
             [0.0, sampling_timer.get(), quant_timer.get(), 0.0],

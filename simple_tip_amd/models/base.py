@@ -7,10 +7,26 @@ leave the device, which is the K15 "AT extraction fused into the forward
 pass" hot path of the MI355X design (no host round-trip, no second model).
 """
 
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
+
+
+class DropoutTail(NamedTuple):
+    """What fused MC-dropout sampling needs from a model whose dropouts all
+    sit behind a deterministic attention prefix (``TapModel.dropout_tail``).
+
+    ``embed`` maps the model input to the block input ``x`` [N, T, E];
+    ``att`` is the block's ``nn.MultiheadAttention`` (own dropout 0), so
+    ``att(x, x, x)[0]`` is the attention output before its dropout;
+    ``params`` is an ``ops.McTransformerParams``; ``rates`` holds the four
+    dropout rates ``(p_attn, p_ffn, p_pool, p_hidden)``."""
+
+    embed: nn.Module
+    att: nn.Module
+    params: tuple
+    rates: Tuple[float, float, float, float]
 
 
 class TapModel(nn.Module):
@@ -74,3 +90,9 @@ class TapModel(nn.Module):
         if sum(isinstance(m, nn.Dropout) for m in self.modules()) != 1:
             return None
         return k, float(drop.p), last
+
+    def dropout_tail(self) -> Optional[DropoutTail]:
+        """A :class:`DropoutTail` if every MC-dropout sample of an input
+        shares a deterministic prefix and differs only in a transformer
+        block's tail (``ops.mc_transformer_votes``). ``None`` by default."""
+        return None

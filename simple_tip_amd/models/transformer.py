@@ -13,7 +13,8 @@ its tuple entries are dead config — see SURVEY.md §2.1).
 import torch
 import torch.nn as nn
 
-from .base import TapModel
+from ..ops.fallback import McTransformerParams
+from .base import DropoutTail, TapModel
 
 
 class TokenAndPositionEmbedding(nn.Module):
@@ -73,3 +74,65 @@ class ImdbTransformer(TapModel):
                 nn.Linear(20, 2),
             ]
         )
+
+    def dropout_tail(self):
+        """The embedding stage, the block's attention, the tail's tensors
+        and the four dropout rates, when the layer list is exactly
+        ``[Identity, embedding, block, pooling, Dropout, Linear + ReLU,
+        Dropout, Linear]`` with a dropout-free attention; else ``None``."""
+        if len(self.layers) != 8:
+            return None
+        ident, emb, blk, pool, drop3, dense, drop4, last = self.layers
+        if not (
+            isinstance(ident, nn.Identity)
+            and isinstance(emb, TokenAndPositionEmbedding)
+            and isinstance(blk, TransformerBlock)
+            and isinstance(pool, _GlobalAveragePooling1D)
+            and isinstance(drop3, nn.Dropout)
+            and isinstance(dense, nn.Sequential)
+            and len(dense) == 2
+            and isinstance(dense[0], nn.Linear)
+            and isinstance(dense[1], nn.ReLU)
+            and isinstance(drop4, nn.Dropout)
+            and isinstance(last, nn.Linear)
+        ):
+            return None
+        att, ffn = blk.att, blk.ffn
+        if not (
+            isinstance(att, nn.MultiheadAttention)
+            and att.dropout == 0.0
+            and att.batch_first
+            and isinstance(ffn, nn.Sequential)
+            and len(ffn) == 3
+            and isinstance(ffn[0], nn.Linear)
+            and isinstance(ffn[1], nn.ReLU)
+            and isinstance(ffn[2], nn.Linear)
+            and isinstance(blk.layernorm1, nn.LayerNorm)
+            and isinstance(blk.layernorm2, nn.LayerNorm)
+            and blk.layernorm1.elementwise_affine
+            and blk.layernorm2.elementwise_affine
+            and blk.layernorm1.eps == blk.layernorm2.eps
+            and isinstance(blk.dropout1, nn.Dropout)
+            and isinstance(blk.dropout2, nn.Dropout)
+        ):
+            return None
+        linears = (ffn[0], ffn[2], dense[0], last)
+        if any(lin.bias is None for lin in linears):
+            return None
+        if blk.layernorm1.bias is None or blk.layernorm2.bias is None:
+            return None
+        # the four dropouts named above must be the only ones
+        if sum(isinstance(m, nn.Dropout) for m in self.modules()) != 4:
+            return None
+        params = McTransformerParams(
+            blk.layernorm1.weight, blk.layernorm1.bias,
+            ffn[0].weight, ffn[0].bias, ffn[2].weight, ffn[2].bias,
+            blk.layernorm2.weight, blk.layernorm2.bias,
+            float(blk.layernorm1.eps),
+            dense[0].weight, dense[0].bias, last.weight, last.bias,
+        )
+        rates = (
+            float(blk.dropout1.p), float(blk.dropout2.p),
+            float(drop3.p), float(drop4.p),
+        )
+        return DropoutTail(emb, att, params, rates)

@@ -203,6 +203,72 @@ def mc_dropout_supported(t: torch.Tensor, C: int, D: int) -> bool:
     return True
 
 
+#: the tensors of a transformer block's stochastic tail (see fallback)
+McTransformerParams = fallback.McTransformerParams
+
+
+def mc_transformer_votes(
+    x: torch.Tensor,
+    attn: torch.Tensor,
+    params: "McTransformerParams",
+    p,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> torch.Tensor:
+    """Votes [N, C] (int32) of ``num_samples`` dropout-masked transformer
+    tails.
+
+    ``x`` [N, T, E] is the block input (the embedding output) and ``attn``
+    [N, T, E] the attention output before its dropout; a sample evaluates
+    ``h = LN1(x + drop1(attn))``, ``y = LN2(h + drop2(FFN(h)))``,
+    ``g = mean_t y``, ``z = relu(W3 drop3(g) + b3)``, ``W4 drop4(z) + b4``
+    with the four rates ``p = (p_attn, p_ffn, p_pool, p_hidden)``. The masks
+    are slices of the stateless generator of :func:`mc_dropout_votes` over
+    one element axis of length ``2*T*E + E + H`` (site offsets ``0``,
+    ``T*E``, ``2*T*E``, ``2*T*E + E``), so the result is reproducible and
+    independent of batching and sharding. On GPU tensors the tail must fit
+    the kernel envelope (E == 32, T <= 128, F <= 64, H <= 64, C <= 4):
+    outside it the call raises ValueError, it never falls back.
+    """
+    return _route(x).mc_transformer_votes(
+        x, attn, params, p, num_samples, seed, row_offset
+    )
+
+
+def mc_transformer_stats(
+    x: torch.Tensor,
+    attn: torch.Tensor,
+    params: "McTransformerParams",
+    p,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(votes int32 [N, C], mean_probs float32 [N, C], mean_entropy
+    float32 [N])`` of the same masked tails as :func:`mc_transformer_votes`
+    (bit-identical votes); the output contract of :func:`mc_dropout_stats`.
+    """
+    return _route(x).mc_transformer_stats(
+        x, attn, params, p, num_samples, seed, row_offset
+    )
+
+
+def mc_transformer_supported(
+    t: torch.Tensor, E: int, T: int, F: int, H: int, C: int
+) -> bool:
+    """Whether a tail of these sizes on ``t``'s device is inside the op's
+    envelope."""
+    impl = _route(t)
+    if impl is fallback:
+        return True
+    try:
+        impl.mc_transformer_check_envelope(E, T, F, H, C)
+    except ValueError:
+        return False
+    return True
+
+
 def nac_profile(acts: torch.Tensor, threshold: float) -> torch.Tensor:
     return _route(acts).nac_profile(acts.contiguous(), threshold)
 

@@ -13,7 +13,7 @@ the reference's row-major ``(N, K, S)`` flattening
 (reference: src/core/neuron_coverage.py:82-94, 118-128).
 """
 
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Tuple
 
 import numpy as np
 import torch
@@ -397,6 +397,221 @@ def mc_dropout_stats(
         feats, weight, bias, p, num_samples, seed, row_offset
     )
     dev = feats.device
+    return votes.to(dev), mean_probs.float().to(dev), mean_entropy.float().to(dev)
+
+
+# ---------------------------------------------------------------------------
+# Fused MC-dropout transformer tail (four dropout sites)
+# ---------------------------------------------------------------------------
+
+
+class McTransformerParams(NamedTuple):
+    """The tensors of a post-LN transformer block's stochastic tail.
+
+    ``w1 [F, E]``/``b1`` and ``w2 [E, F]``/``b2`` are the feed-forward pair,
+    ``w3 [H, E]``/``b3`` the hidden Dense and ``w4 [C, H]``/``b4`` the output
+    Dense; both LayerNorms share ``eps`` (a python float)."""
+
+    ln1_w: torch.Tensor
+    ln1_b: torch.Tensor
+    w1: torch.Tensor
+    b1: torch.Tensor
+    w2: torch.Tensor
+    b2: torch.Tensor
+    ln2_w: torch.Tensor
+    ln2_b: torch.Tensor
+    eps: float
+    w3: torch.Tensor
+    b3: torch.Tensor
+    w4: torch.Tensor
+    b4: torch.Tensor
+
+
+def mc_transformer_dims(x, attn, params) -> Tuple[int, int, int, int, int, int]:
+    """``(N, T, E, F, H, C)`` of a tail call; ValueError on a shape mismatch."""
+    if x.dim() != 3 or attn.shape != x.shape:
+        raise ValueError("expected x and attn of one shape [N, T, E]")
+    n, t, e = x.shape
+    if params.w1.dim() != 2 or params.w3.dim() != 2 or params.w4.dim() != 2:
+        raise ValueError("w1, w3 and w4 must be 2-D")
+    f, h, c = params.w1.shape[0], params.w3.shape[0], params.w4.shape[0]
+    want = {
+        "ln1_w": (e,), "ln1_b": (e,), "w1": (f, e), "b1": (f,),
+        "w2": (e, f), "b2": (e,), "ln2_w": (e,), "ln2_b": (e,),
+        "w3": (h, e), "b3": (h,), "w4": (c, h), "b4": (c,),
+    }
+    for name, shape in want.items():
+        got = tuple(getattr(params, name).shape)
+        if got != shape:
+            raise ValueError(f"params.{name} must be {shape}, got {got}")
+    if min(t, e, f, h, c) < 1:
+        raise ValueError("T, E, F, H and C must be at least 1")
+    return n, t, e, f, h, c
+
+
+def _mc_transformer_rates(p) -> Tuple[float, float, float, float]:
+    p = tuple(float(v) for v in p)
+    if len(p) != 4:
+        raise ValueError("p must hold the four rates (attn, ffn, pool, hidden)")
+    return p
+
+
+def mc_transformer_masks(
+    seed: int, S: int, N: int, T: int, E: int, H: int, p, row_offset: int = 0
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Keep masks of the four dropout sites, bool ``[S, N, T, E]``,
+    ``[S, N, T, E]``, ``[S, N, E]`` and ``[S, N, H]``.
+
+    The sites share the flat element axis of one :func:`dropout_words` call
+    of length ``2*T*E + E + H``: the attention dropout at ``t*E + e``, the
+    feed-forward dropout at ``T*E + t*E + e``, the pooled dropout at
+    ``2*T*E + e`` and the hidden dropout at ``2*T*E + E + h``."""
+    p = _mc_transformer_rates(p)
+    te = T * E
+    words = dropout_words(seed, S, N, 2 * te + E + H, row_offset)
+    th = [dropout_threshold(v) for v in p]
+    return (
+        (words[:, :, :te] >= th[0]).reshape(S, N, T, E),
+        (words[:, :, te : 2 * te] >= th[1]).reshape(S, N, T, E),
+        words[:, :, 2 * te : 2 * te + E] >= th[2],
+        words[:, :, 2 * te + E :] >= th[3],
+    )
+
+
+def _layer_norm(v, w, b, eps):
+    """LayerNorm over the last axis with the biased variance."""
+    d = v - v.mean(dim=-1, keepdim=True)
+    var = (d * d).mean(dim=-1, keepdim=True)
+    return d / torch.sqrt(var + eps) * w + b
+
+
+def _mc_transformer_logits(x, attn, q, masks, scales) -> torch.Tensor:
+    """Logits [S, N, C] of the masked tails in the dtype of ``x``: ``x`` and
+    ``attn`` [N, T, E], ``masks`` the four keep masks of
+    :func:`mc_transformer_masks`, ``scales`` the four ``dropout_scale``."""
+    lin = torch.nn.functional.linear
+    dtype = x.dtype
+    k1, k2, k3, k4 = masks
+    hid = _layer_norm(
+        x[None] + (k1.to(dtype) * scales[0]) * attn[None],
+        q.ln1_w, q.ln1_b, q.eps,
+    )  # [S, N, T, E]
+    ffn = lin(torch.relu(lin(hid, q.w1, q.b1)), q.w2, q.b2)
+    y = _layer_norm(
+        hid + (k2.to(dtype) * scales[1]) * ffn, q.ln2_w, q.ln2_b, q.eps
+    )
+    g = y.mean(dim=2)  # [S, N, E]
+    z = torch.relu(lin((k3.to(dtype) * scales[2]) * g, q.w3, q.b3))
+    return lin((k4.to(dtype) * scales[3]) * z, q.w4, q.b4)
+
+
+def _mc_transformer_eval(x, attn, params, p, num_samples, seed, row_offset,
+                         with_stats: bool, dtype=torch.float32):
+    """Shared body of mc_transformer_votes / mc_transformer_stats.
+
+    Returns ``(votes int32 [N, C], mean_probs float64 [N, C] | None,
+    mean_entropy float64 [N] | None)`` on the CPU. The logits are evaluated
+    in ``dtype``; the statistics are computed from them in float64. A site's
+    dropout is ``v + scale * keep * u`` with ``scale * keep`` exact, so the
+    product and the sum are rounded separately.
+    """
+    n, t, e, f, h, c = mc_transformer_dims(x, attn, params)
+    S = int(num_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"num_samples must be in [1, 65535], got {S}")
+    if row_offset < 0 or row_offset + n > 2 ** 32:
+        raise ValueError("rows must satisfy row_offset + N <= 2^32")
+    p = _mc_transformer_rates(p)
+    for v in p:
+        dropout_threshold(v)  # range check
+    sc = [dropout_scale(v) for v in p]
+
+    def cpu(v):
+        return v.detach().to("cpu", dtype)
+
+    xs, at = cpu(x), cpu(attn)
+    q = McTransformerParams(*[
+        float(v) if name == "eps" else cpu(v)
+        for name, v in zip(McTransformerParams._fields, params)
+    ])
+    votes = torch.zeros(n, c, dtype=torch.int32)
+    mean_probs = torch.zeros(n, c, dtype=torch.float64) if with_stats else None
+    mean_entropy = torch.zeros(n, dtype=torch.float64) if with_stats else None
+    dtot = 2 * t * e + e + h
+    rows = max(1, _MCD_MAX_MASK_ELEMS // max(1, S * dtot))
+    ones = torch.ones(1, dtype=torch.int32)
+    cls = torch.arange(c, dtype=torch.int64)
+    for s0 in range(0, n, rows):
+        xb, ab = xs[s0 : s0 + rows], at[s0 : s0 + rows]
+        nb = xb.shape[0]
+        k1, k2, k3, k4 = mc_transformer_masks(
+            seed, S, nb, t, e, h, p, row_offset + s0
+        )
+        logits = _mc_transformer_logits(xb, ab, q, (k1, k2, k3, k4), sc)
+        is_max = logits == logits.max(dim=2, keepdim=True).values
+        best = torch.where(is_max, cls, c).min(dim=2).values  # [S, nb]
+        best.clamp_(max=c - 1)
+        votes[s0 : s0 + nb].scatter_add_(
+            1, best.t().contiguous(), ones.expand(nb, S)
+        )
+        if with_stats:
+            v = logits.double()
+            v = v - v.max(dim=2, keepdim=True).values
+            ex = torch.exp(v)
+            zsum = ex.sum(dim=2, keepdim=True)
+            probs = ex / zsum
+            ent = torch.log(zsum.squeeze(2)) - (probs * v).sum(dim=2)
+            mean_probs[s0 : s0 + nb] = probs.mean(dim=0)
+            mean_entropy[s0 : s0 + nb] = ent.mean(dim=0)
+    return votes, mean_probs, mean_entropy
+
+
+def mc_transformer_votes(
+    x: torch.Tensor,
+    attn: torch.Tensor,
+    params: McTransformerParams,
+    p,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> torch.Tensor:
+    """Argmax votes of ``num_samples`` dropout-masked transformer tails,
+    int32 [N, C]: float32 logits from torch ops over row chunks of at most
+    ``_MCD_MAX_MASK_ELEMS`` mask elements; the vote goes to the lowest index
+    among the maximal logits."""
+    votes, _, _ = _mc_transformer_eval(
+        x, attn, params, p, num_samples, seed, row_offset, with_stats=False
+    )
+    return votes.to(x.device)
+
+
+def _mc_transformer_stats_f64(
+    x, attn, params, p, num_samples, seed, row_offset=0
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(votes int32, mean_probs float64, mean_entropy float64) with the
+    whole tail, the logits included, evaluated in float64; for tests."""
+    return _mc_transformer_eval(
+        x, attn, params, p, num_samples, seed, row_offset, with_stats=True,
+        dtype=torch.float64,
+    )
+
+
+def mc_transformer_stats(
+    x: torch.Tensor,
+    attn: torch.Tensor,
+    params: McTransformerParams,
+    p,
+    num_samples: int,
+    seed: int,
+    row_offset: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Votes, mean softmax and mean per-sample entropy of the masked tails:
+    the float32 logits (and votes) of :func:`mc_transformer_votes`, the
+    statistics from them in float64, rounded to float32 once."""
+    votes, mean_probs, mean_entropy = _mc_transformer_eval(
+        x, attn, params, p, num_samples, seed, row_offset, with_stats=True
+    )
+    dev = x.device
     return votes.to(dev), mean_probs.float().to(dev), mean_entropy.float().to(dev)
 
 

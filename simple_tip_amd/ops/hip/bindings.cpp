@@ -104,6 +104,13 @@ int mc_dropout_max_grid(int, int);
 int mc_dropout_rows_per_block();
 int mc_dropout_max_classes();
 int mc_dropout_max_features();
+void launch_mc_transformer(const float*, const float*, const float* const*,
+                           float, const uint32_t*, const float*, int, int, int,
+                           int, int, int, uint32_t, uint32_t, uint32_t, int*,
+                           float*, float*, bool, hipStream_t);
+int mc_transformer_max_grid(int, int, int);
+int mc_transformer_lds_bytes(int, int, int);
+void mc_transformer_limits(int*);
 
 namespace {
 
@@ -867,6 +874,88 @@ std::vector<torch::Tensor> mc_dropout_stats(
   return {votes, mean_probs, mean_entropy};
 }
 
+// ---- fused MC-dropout transformer tail (four dropout sites) ----
+
+// {E, max T, max F, max H, max C} of the kernel envelope.
+std::vector<int64_t> mc_transformer_envelope() {
+  int lim[5];
+  mc_transformer_limits(lim);
+  return {lim[0], lim[1], lim[2], lim[3], lim[4]};
+}
+
+// params: ln1_w, ln1_b, w1 [F,E], b1, w2 [E,F], b2, ln2_w, ln2_b, w3 [H,E],
+// b3, w4 [C,H], b4. Returns {votes} or {votes, mean_probs, mean_entropy}.
+std::vector<torch::Tensor> mc_transformer(
+    torch::Tensor x, torch::Tensor attn, std::vector<torch::Tensor> params,
+    double eps, std::vector<int64_t> thresh, std::vector<double> scale,
+    int64_t num_samples, int64_t seed_lo, int64_t seed_hi, int64_t row_offset,
+    bool with_stats) {
+  int lim[5];
+  mc_transformer_limits(lim);
+  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kFloat32 && x.dim() == 3 &&
+                  x.is_contiguous(),
+              "x must be a contiguous [N, T, E] fp32 GPU tensor");
+  TORCH_CHECK(attn.is_cuda() && attn.dtype() == torch::kFloat32 &&
+                  attn.is_contiguous() && attn.sizes() == x.sizes(),
+              "attn must be a contiguous fp32 GPU tensor shaped like x");
+  TORCH_CHECK(params.size() == 12 && thresh.size() == 4 && scale.size() == 4,
+              "expected 12 parameter tensors and 4 rates");
+  const int64_t n = x.size(0), t = x.size(1), e = x.size(2);
+  for (const auto& p : params)
+    TORCH_CHECK(p.is_cuda() && p.dtype() == torch::kFloat32 &&
+                    p.is_contiguous() && p.dim() >= 1 && p.dim() <= 2,
+                "parameters must be contiguous fp32 GPU tensors");
+  TORCH_CHECK(params[2].dim() == 2 && params[8].dim() == 2 &&
+                  params[10].dim() == 2,
+              "w1, w3 and w4 must be 2-D");
+  const int64_t f = params[2].size(0), h = params[8].size(0),
+                c = params[10].size(0);
+  TORCH_CHECK(e == lim[0] && t >= 1 && t <= lim[1] && f >= 1 && f <= lim[2] &&
+                  h >= 1 && h <= lim[3] && c >= 1 && c <= lim[4],
+              "mc_transformer envelope is E == ", lim[0], ", T <= ", lim[1],
+              ", F <= ", lim[2], ", H <= ", lim[3], ", C <= ", lim[4]);
+  const int64_t want[12][2] = {{e, 0}, {e, 0}, {f, e}, {f, 0}, {e, f}, {e, 0},
+                               {e, 0}, {e, 0}, {h, e}, {h, 0}, {c, h}, {c, 0}};
+  for (int i = 0; i < 12; ++i) {
+    const bool two = want[i][1] != 0;
+    TORCH_CHECK(params[i].dim() == (two ? 2 : 1) &&
+                    params[i].size(0) == want[i][0] &&
+                    (!two || params[i].size(1) == want[i][1]),
+                "parameter ", i, " has the wrong shape");
+  }
+  TORCH_CHECK(num_samples >= 1 && num_samples <= 65535, "bad num_samples");
+  uint32_t th[4];
+  float sc[4];
+  for (int i = 0; i < 4; ++i) {
+    TORCH_CHECK(thresh[i] >= 0 && thresh[i] <= 0xFFFFFFFFll, "bad threshold");
+    th[i] = (uint32_t)thresh[i];
+    sc[i] = (float)scale[i];
+  }
+  TORCH_CHECK(n <= 0x7FFFFFFFll && row_offset >= 0 &&
+                  row_offset + n <= 0x100000000ll,
+              "rows must satisfy row_offset + N <= 2^32");
+  auto votes = torch::empty({n, c}, x.options().dtype(torch::kInt32));
+  torch::Tensor mean_probs, mean_entropy;
+  if (with_stats) {
+    mean_probs = torch::empty({n, c}, x.options());
+    mean_entropy = torch::empty({n}, x.options());
+  }
+  if (n > 0) {
+    const float* ptrs[12];
+    for (int i = 0; i < 12; ++i) ptrs[i] = params[i].data_ptr<float>();
+    launch_mc_transformer(
+        x.data_ptr<float>(), attn.data_ptr<float>(), ptrs, (float)eps, th, sc,
+        (int)n, (int)t, (int)f, (int)h, (int)c, (int)num_samples,
+        (uint32_t)seed_lo, (uint32_t)seed_hi, (uint32_t)row_offset,
+        votes.data_ptr<int>(),
+        with_stats ? mean_probs.data_ptr<float>() : nullptr,
+        with_stats ? mean_entropy.data_ptr<float>() : nullptr, with_stats,
+        cur_stream());
+  }
+  if (with_stats) return {votes, mean_probs, mean_entropy};
+  return {votes};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -919,4 +1008,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mc_dropout_rows_per_block", &mc_dropout_rows_per_block);
   m.def("mc_dropout_max_classes", &mc_dropout_max_classes);
   m.def("mc_dropout_max_features", &mc_dropout_max_features);
+  m.def("mc_transformer", &mc_transformer);
+  m.def("mc_transformer_envelope", &mc_transformer_envelope);
+  m.def("mc_transformer_max_grid", &mc_transformer_max_grid);
+  m.def("mc_transformer_lds_bytes", &mc_transformer_lds_bytes);
 }

@@ -64,15 +64,6 @@ static void mcd_check(hipError_t e, const char* what) {
                              hipGetErrorString(e));
 }
 
-TIP_DEV uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
 template <int CP, bool STATS>
 __global__ __launch_bounds__(MCD_THREADS) void mc_dropout_votes_kernel(
     const float* __restrict__ feats, const float* __restrict__ weight,

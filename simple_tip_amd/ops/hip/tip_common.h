@@ -41,3 +41,14 @@ TIP_DEV float half_reduce_sum(float v) {
   for (int off = 16; off >= 1; off >>= 1) v += __shfl_xor(v, off);
   return v;
 }
+
+// 32-bit finalizer of the stateless dropout-mask generator (mcdropout.hip,
+// mctail.hip; ops/fallback.py::_mix32). Unsigned, wrapping.
+TIP_DEV uint32_t mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}

@@ -174,6 +174,102 @@ def mc_dropout_stats(
     return votes, mean_probs, mean_entropy
 
 
+#: device envelope of the fused transformer tail (mctail.hip): the embedding
+#: width is fixed, the row's x / attn and the parameters must fit in LDS
+(
+    MC_TRANSFORMER_EMBED,
+    MC_TRANSFORMER_MAX_TOKENS,
+    MC_TRANSFORMER_MAX_FF,
+    MC_TRANSFORMER_MAX_HIDDEN,
+    MC_TRANSFORMER_MAX_CLASSES,
+) = _ext.mc_transformer_envelope()
+
+
+def mc_transformer_launch_config(T: int, F: int, H: int) -> Dict[str, int]:
+    """Launch constants of ``mc_transformer_votes`` on the current device.
+
+    One block handles one row at a time; the grid is capped at ``max_grid``
+    blocks, so ``rows_per_pass`` rows are in flight and the grid-stride row
+    loop runs ``ceil(N / rows_per_pass)`` passes.
+    """
+    max_grid = _ext.mc_transformer_max_grid(int(T), int(F), int(H))
+    return {
+        "rows_per_block": 1,
+        "max_grid": max_grid,
+        "rows_per_pass": max_grid,
+        "lds_bytes": _ext.mc_transformer_lds_bytes(int(T), int(F), int(H)),
+    }
+
+
+def mc_transformer_check_envelope(E: int, T: int, F: int, H: int, C: int) -> None:
+    """Raise ValueError if a tail of these sizes is outside the envelope."""
+    if not (
+        E == MC_TRANSFORMER_EMBED
+        and 1 <= T <= MC_TRANSFORMER_MAX_TOKENS
+        and 1 <= F <= MC_TRANSFORMER_MAX_FF
+        and 1 <= H <= MC_TRANSFORMER_MAX_HIDDEN
+        and 1 <= C <= MC_TRANSFORMER_MAX_CLASSES
+    ):
+        raise ValueError(
+            f"mc_transformer_votes on GPU supports E == {MC_TRANSFORMER_EMBED}, "
+            f"T <= {MC_TRANSFORMER_MAX_TOKENS}, F <= {MC_TRANSFORMER_MAX_FF}, "
+            f"H <= {MC_TRANSFORMER_MAX_HIDDEN}, C <= {MC_TRANSFORMER_MAX_CLASSES} "
+            f"(got E={E}, T={T}, F={F}, H={H}, C={C})"
+        )
+
+
+def _mc_transformer(x, attn, params, p, num_samples, seed, row_offset, stats):
+    """Validate and convert the arguments, then launch."""
+    from . import fallback
+
+    n, t, e, f, h, c = fallback.mc_transformer_dims(x, attn, params)
+    mc_transformer_check_envelope(e, t, f, h, c)
+    S = int(num_samples)
+    if not 1 <= S <= 65535:
+        raise ValueError(f"num_samples must be in [1, 65535], got {S}")
+    row_offset = int(row_offset)
+    if row_offset < 0 or row_offset + n > 2 ** 32:
+        raise ValueError("rows must satisfy row_offset + N <= 2^32")
+    rates = fallback._mc_transformer_rates(p)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    dev = x.device
+    tensors = [
+        v.to(dev).float().contiguous()
+        for name, v in zip(params._fields, params)
+        if name != "eps"
+    ]
+    return _ext.mc_transformer(
+        x.float().contiguous(),
+        attn.to(dev).float().contiguous(),
+        tensors,
+        float(params.eps),
+        [fallback.dropout_threshold(v) for v in rates],
+        [fallback.dropout_scale(v) for v in rates],
+        S,
+        seed & 0xFFFFFFFF,
+        seed >> 32,
+        row_offset,
+        stats,
+    )
+
+
+def mc_transformer_votes(
+    x, attn, params, p, num_samples: int, seed: int, row_offset: int = 0
+) -> torch.Tensor:
+    return _mc_transformer(
+        x, attn, params, p, num_samples, seed, row_offset, False
+    )[0]
+
+
+def mc_transformer_stats(
+    x, attn, params, p, num_samples: int, seed: int, row_offset: int = 0
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    votes, mean_probs, mean_entropy = _mc_transformer(
+        x, attn, params, p, num_samples, seed, row_offset, True
+    )
+    return votes, mean_probs, mean_entropy
+
+
 #: Cap on the centred workspace of one grouped-Gaussian launch, in bytes
 #: (``slots * padded_rows * D * 4``). A batch whose workspace would be larger
 #: is scored in row chunks; per-row results do not depend on the batch a row
