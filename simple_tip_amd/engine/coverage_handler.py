@@ -8,13 +8,16 @@ and the CAM greedy loop runs on the device bitmap (ops.cam_order).
 """
 
 import logging
+import os
 from typing import Callable, Dict, List, Tuple
 
 import numpy as np
 import torch
 
 from ..core.bitmap import BitProfile
-from ..core.neuron_coverage import KMNC, NAC, NBC, SNAC, TKNC, CoverageMethod
+from ..core.neuron_coverage import (
+    KMNC, NAC, NBC, SNAC, TKNC, CoverageMethod, CoverageSuite,
+)
 from ..core.prioritizers import cam
 from ..core.timer import DeviceTimer
 from .model_handler import BaseModel, iter_batches
@@ -31,12 +34,35 @@ class CoverageWorker:
     ``evaluate_all`` profiles this rank's test shard, reassembling the full
     profile matrix with the coverage-bitmap OR all-reduce (BASELINE
     config 4) so scores and the CAM order are identical on every rank.
+
+    ``nc_mode="fused"`` scores every batch with one
+    :class:`~simple_tip_amd.core.neuron_coverage.CoverageSuite` call instead
+    of one call per metric (``"per_metric"``, the default); scores, profiles
+    and CAM orders are identical. ``TIP_NC_MODE`` overrides the argument.
+    Time accounting in fused mode is deliberately conservative: every
+    metric's ``quant`` slot is charged the WHOLE suite call, since on this
+    path no metric could have been computed alone for less, so no table
+    ever understates a metric's cost (the slots therefore do not add up to
+    the wall time). ``pred`` is charged as in the per-metric mode.
     """
 
-    def __init__(self, base_model: BaseModel, training_set, dist_shard: bool = False):
+    def __init__(
+        self,
+        base_model: BaseModel,
+        training_set,
+        dist_shard: bool = False,
+        nc_mode: str = "per_metric",
+    ):
         from ..parallel.dist import get_world_size, shard_slice
         from .aggregate_statistics import AggregateStatisticsCollector
 
+        nc_mode = os.environ.get("TIP_NC_MODE", nc_mode)
+        if nc_mode not in ("per_metric", "fused"):
+            raise ValueError(
+                f"nc_mode must be 'per_metric' or 'fused', got {nc_mode!r}"
+            )
+        self.nc_mode = nc_mode
+        self._suite = None
         self.base_model = base_model
         self.dist_shard = bool(dist_shard) and get_world_size() > 1
         self.metrics: Dict[str, CoverageMethod] = {}
@@ -130,6 +156,18 @@ class CoverageWorker:
             except StopIteration:
                 break
             pred_time = t.get()
+            if self.nc_mode == "fused":
+                if self._suite is None:
+                    self._suite = CoverageSuite(self.metrics)
+                qt = DeviceTimer()
+                with qt:
+                    fused = self._suite(acts)
+                for metric_id, (s, p) in fused.items():
+                    times[metric_id][1] += pred_time
+                    times[metric_id][2] += qt.get()  # the whole call, each
+                    scores_parts[metric_id].append(s)
+                    profile_parts[metric_id].append(p)
+                continue
             for metric_id, metric in self.metrics.items():
                 qt = DeviceTimer()
                 with qt:

@@ -295,5 +295,53 @@ def tknc_profile(layer_acts: List[torch.Tensor], k: int) -> torch.Tensor:
     )
 
 
+def coverage_suite(
+    layers: List[torch.Tensor],
+    nac_thresholds: Tuple[float, ...] = (),
+    upper_bounds: torch.Tensor = None,
+    nbc_lower: torch.Tensor = None,
+    nbc_upper: torch.Tensor = None,
+    kmnc_mins: torch.Tensor = None,
+    kmnc_maxs: torch.Tensor = None,
+    kmnc_sections: Tuple[int, ...] = (),
+    tknc_ks: Tuple[int, ...] = (),
+) -> Dict[str, List[Tuple[torch.Tensor, torch.Tensor]]]:
+    """Every requested NAC / SNAC / NBC / KMNC / TKNC profile of one batch.
+
+    ``layers`` are the tapped layers as fp32 contiguous [N, K_l] tensors,
+    NOT concatenated; the neuron axis of every table (``upper_bounds``
+    [U, K], ``nbc_lower`` / ``nbc_upper`` [B, K], ``kmnc_mins`` /
+    ``kmnc_maxs`` [K]) is their concatenation order. Returns
+    ``{family: [(words int64 [N, W], scores int64 [N]), ...]}`` for the
+    families ``nac``, ``snac``, ``nbc``, ``kmnc``, ``tknc``, one entry per
+    threshold / table row / section count / k, with the bit layouts of the
+    per-metric ops and ``scores == popcount_rows(words)``. Any family may be
+    empty.
+
+    Every word equals what :func:`nac_profile`, :func:`snac_profile`,
+    :func:`nbc_profile`, :func:`kmnc_profile` and :func:`tknc_profile`
+    return for the concatenated input, for every input. On GPU tensors two
+    launches read the layers where they lie (once for the threshold
+    families, once for top-k) and a row's words do not depend on the batch
+    it arrives in. Outside the envelope (more than 8 layers, more than 4
+    entries in a family, a section count outside 1..16, a k outside 1..4,
+    layers of different N, a table whose width is not K) the call raises
+    ValueError, it never falls back.
+    """
+    return _route(layers[0]).coverage_suite(
+        layers, nac_thresholds, upper_bounds, nbc_lower, nbc_upper,
+        kmnc_mins, kmnc_maxs, kmnc_sections, tknc_ks,
+    )
+
+
+def coverage_suite_chunk() -> int:
+    """Neurons of the concatenated axis that one block of the GPU suite
+    kernel owns (a multiple of 64); needs the HIP extension."""
+    ext = _load_ext()
+    if ext is None:
+        raise RuntimeError(f"HIP extension not importable: {_EXT_ERR!r}")
+    return ext.coverage_suite_chunk()
+
+
 def bucketize_profile(values: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
     return _route(values).bucketize_profile(values, thresholds)

@@ -685,6 +685,54 @@ def tknc_profile(layer_acts, k: int) -> torch.Tensor:
     return pack_bits(torch.cat(parts, dim=1))
 
 
+#: profile families of :func:`coverage_suite`, in output order
+COVERAGE_SUITE_FAMILIES = ("nac", "snac", "nbc", "kmnc", "tknc")
+
+
+def coverage_suite(
+    layers,
+    nac_thresholds=(),
+    upper_bounds=None,
+    nbc_lower=None,
+    nbc_upper=None,
+    kmnc_mins=None,
+    kmnc_maxs=None,
+    kmnc_sections=(),
+    tknc_ks=(),
+):
+    """Every requested coverage profile of one batch of tapped layers.
+
+    ``layers`` is a list of [N, K_l] tensors; the neuron axis of every table
+    is their concatenation order. Returns ``{family: [(words, scores), ...]}``
+    for the families ``nac`` (one entry per threshold), ``snac`` (per row of
+    ``upper_bounds`` [U, K]), ``nbc`` (per row of ``nbc_lower`` /
+    ``nbc_upper`` [B, K]), ``kmnc`` (per entry of ``kmnc_sections``) and
+    ``tknc`` (per entry of ``tknc_ks``), with ``scores`` the popcount of
+    ``words``. This composes the per-metric functions above, so it defines
+    what the fused HIP op must return word for word.
+    """
+    layers = [l.reshape(l.shape[0], -1) for l in layers]
+    acts = torch.cat(layers, dim=1)
+
+    def entry(words):
+        return words, popcount_rows(words)
+
+    out = {f: [] for f in COVERAGE_SUITE_FAMILIES}
+    for thr in nac_thresholds:
+        out["nac"].append(entry(nac_profile(acts, float(thr))))
+    for u in range(0 if upper_bounds is None else upper_bounds.shape[0]):
+        out["snac"].append(entry(snac_profile(acts, upper_bounds[u])))
+    for b in range(0 if nbc_lower is None else nbc_lower.shape[0]):
+        out["nbc"].append(entry(nbc_profile(acts, nbc_lower[b], nbc_upper[b])))
+    for sections in kmnc_sections:
+        out["kmnc"].append(
+            entry(kmnc_profile(acts, kmnc_mins, kmnc_maxs, int(sections)))
+        )
+    for k in tknc_ks:
+        out["tknc"].append(entry(tknc_profile(layers, int(k))))
+    return out
+
+
 def bucketize_profile(values: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
     """Surprise-coverage binning: bit s set iff thr[s] <= v < thr[s+1].
 

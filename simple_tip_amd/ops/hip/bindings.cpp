@@ -9,7 +9,10 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <vector>
+
+#include "coverage_suite.h"
 
 // launchers defined in the .hip translation units
 void launch_rownorm(const float*, int, int, float*, hipStream_t);
@@ -956,6 +959,139 @@ std::vector<torch::Tensor> mc_transformer(
   return {votes};
 }
 
+// ---- fused coverage suite (coverage_suite.hip) ----
+
+// Every NAC / SNAC / NBC / KMNC / TKNC profile of `layers` ([N, K_l] fp32
+// each, not concatenated) in two launches. Returns one words tensor per
+// profile in the order NAC, SNAC, NBC, KMNC, TKNC, then scores [profiles, N].
+// The Python wrapper checks the envelope and raises ValueError; the checks
+// here guard the kernels' indexing.
+std::vector<torch::Tensor> coverage_suite(
+    std::vector<torch::Tensor> layers, std::vector<double> nac_thresholds,
+    torch::Tensor snac_hi, torch::Tensor nbc_lo, torch::Tensor nbc_hi,
+    torch::Tensor kmnc_lo, torch::Tensor kmnc_hi,
+    std::vector<int64_t> kmnc_sections, std::vector<int64_t> tknc_ks) {
+  const int64_t L = layers.size();
+  TORCH_CHECK(L >= 1 && L <= SUITE_MAX_LAYERS, "coverage_suite takes 1..",
+              SUITE_MAX_LAYERS, " layers");
+  const int64_t n = layers[0].size(0);
+  SuiteArgs a = {};
+  SuiteTopkArgs tk = {};
+  int64_t K = 0;
+  for (int64_t l = 0; l < SUITE_MAX_LAYERS; ++l) {
+    a.off[l] = tk.off[l] = INT_MAX;
+    if (l >= L) continue;
+    check_f32_2d(layers[l], "layer");
+    TORCH_CHECK(layers[l].size(0) == n, "layers must share N");
+    a.layer[l] = tk.layer[l] = layers[l].data_ptr<float>();
+    a.off[l] = tk.off[l] = (int)K;
+    a.width[l] = tk.width[l] = (int)layers[l].size(1);
+    K += layers[l].size(1);
+    TORCH_CHECK(K * SUITE_MAX_SECTIONS < INT_MAX, "too many neurons");
+  }
+  TORCH_CHECK(n < INT_MAX, "too many rows");
+  TORCH_CHECK((K + coverage_suite_chunk() - 1) / coverage_suite_chunk() <= 65535,
+              "too many neurons");
+  const int64_t n_nac = nac_thresholds.size(), n_kmnc = kmnc_sections.size();
+  const int64_t n_tknc = tknc_ks.size();
+  const int64_t n_snac = snac_hi.numel() ? snac_hi.size(0) : 0;
+  const int64_t n_nbc = nbc_lo.numel() ? nbc_lo.size(0) : 0;
+  TORCH_CHECK(n_nac <= SUITE_MAX_FAMILY && n_snac <= SUITE_MAX_FAMILY &&
+                  n_nbc <= SUITE_MAX_FAMILY && n_kmnc <= SUITE_MAX_FAMILY &&
+                  n_tknc <= SUITE_MAX_FAMILY,
+              "at most ", SUITE_MAX_FAMILY, " profiles per family");
+  if (n_snac) check_dev(snac_hi, torch::kFloat32, n_snac * K, "upper_bounds");
+  if (n_nbc) {
+    check_dev(nbc_lo, torch::kFloat32, n_nbc * K, "nbc_lower");
+    check_dev(nbc_hi, torch::kFloat32, n_nbc * K, "nbc_upper");
+  }
+  if (n_kmnc) {
+    check_dev(kmnc_lo, torch::kFloat32, K, "kmnc_mins");
+    check_dev(kmnc_hi, torch::kFloat32, K, "kmnc_maxs");
+  }
+  for (int64_t s : kmnc_sections)
+    TORCH_CHECK(s >= 1 && s <= SUITE_MAX_SECTIONS, "kmnc sections in 1..",
+                SUITE_MAX_SECTIONS);
+  for (int64_t k : tknc_ks)
+    TORCH_CHECK(k >= 1 && k <= SUITE_MAX_TOPK, "tknc k in 1..", SUITE_MAX_TOPK);
+
+  // words per row of every profile, in output order
+  const int64_t w_flat = (K + 63) / 64;
+  std::vector<int64_t> widths;
+  for (int64_t i = 0; i < n_nac + n_snac; ++i) widths.push_back(w_flat);
+  for (int64_t i = 0; i < n_nbc; ++i) widths.push_back((2 * K + 63) / 64);
+  for (int64_t s : kmnc_sections) widths.push_back((K * s + 63) / 64);
+  const int64_t n_thr = widths.size(), n_prof = n_thr + n_tknc;
+  int64_t thr_words = 0;
+  for (int64_t w : widths) thr_words += n * w;
+
+  // the threshold kernel writes every word it owns; scores and the TKNC
+  // words are accumulated into, so they start at zero (one fill for both)
+  auto iopts = layers[0].options().dtype(torch::kInt64);
+  auto thr_buf = torch::empty({thr_words}, iopts);
+  auto zero_buf = torch::zeros({n_prof * n + n_tknc * n * w_flat}, iopts);
+  auto scores = zero_buf.narrow(0, 0, n_prof * n).view({n_prof, n});
+  std::vector<torch::Tensor> out;
+  int64_t at = 0;
+  for (int64_t i = 0; i < n_thr; ++i) {
+    out.push_back(thr_buf.narrow(0, at, n * widths[i]).view({n, widths[i]}));
+    at += n * widths[i];
+  }
+  for (int64_t t = 0; t < n_tknc; ++t)
+    out.push_back(zero_buf.narrow(0, n_prof * n + t * n * w_flat, n * w_flat)
+                      .view({n, w_flat}));
+  out.push_back(scores);
+  if (n == 0 || K == 0) return out;
+
+  auto wptr = [](torch::Tensor& t) {
+    return reinterpret_cast<unsigned long long*>(t.data_ptr<int64_t>());
+  };
+  if (n_thr > 0) {
+    a.rows = (int)n;
+    a.K = (int)K;
+    a.n_nac = (int)n_nac;
+    a.n_snac = (int)n_snac;
+    a.n_nbc = (int)n_nbc;
+    a.n_kmnc = (int)n_kmnc;
+    int64_t p = 0;
+    for (int64_t i = 0; i < n_nac; ++i) {
+      a.nac_thr[i] = static_cast<float>(nac_thresholds[i]);
+      a.words[i] = wptr(out[p++]);
+    }
+    for (int64_t i = 0; i < n_snac; ++i)
+      a.words[SUITE_MAX_FAMILY + i] = wptr(out[p++]);
+    for (int64_t i = 0; i < n_nbc; ++i)
+      a.words[2 * SUITE_MAX_FAMILY + i] = wptr(out[p++]);
+    for (int64_t i = 0; i < n_kmnc; ++i) {
+      a.kmnc_sec[i] = (int)kmnc_sections[i];
+      a.words[3 * SUITE_MAX_FAMILY + i] = wptr(out[p++]);
+    }
+    a.snac_hi = n_snac ? snac_hi.data_ptr<float>() : nullptr;
+    a.nbc_lo = n_nbc ? nbc_lo.data_ptr<float>() : nullptr;
+    a.nbc_hi = n_nbc ? nbc_hi.data_ptr<float>() : nullptr;
+    a.kmnc_lo = n_kmnc ? kmnc_lo.data_ptr<float>() : nullptr;
+    a.kmnc_hi = n_kmnc ? kmnc_hi.data_ptr<float>() : nullptr;
+    a.scores = reinterpret_cast<long long*>(scores.data_ptr<int64_t>());
+    launch_coverage_suite_threshold(a, cur_stream());
+  }
+  if (n_tknc > 0) {
+    tk.rows = (int)n;
+    tk.L = (int)L;
+    tk.W = (int)w_flat;
+    tk.n = (int)n_tknc;
+    for (int64_t t = 0; t < n_tknc; ++t) {
+      tk.k[t] = (int)tknc_ks[t];
+      tk.words[t] = wptr(out[n_thr + t]);
+      tk.scores[t] = reinterpret_cast<long long*>(scores.data_ptr<int64_t>()) +
+                     (n_thr + t) * n;
+    }
+    launch_coverage_suite_topk(tk, cur_stream());
+  }
+  return out;
+}
+
+int64_t coverage_suite_chunk_py() { return coverage_suite_chunk(); }
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -992,6 +1128,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("popcount_rows", &popcount_rows);
   m.def("tknc_layer", &tknc_layer);
   m.def("bucketize", &bucketize);
+  m.def("coverage_suite", &coverage_suite);
+  m.def("coverage_suite_chunk", &coverage_suite_chunk_py);
   m.def("cam_greedy", &cam_greedy);
   m.def("softmax_scores", &softmax_scores);
   m.def("levenshtein_matrix", &levenshtein_matrix);

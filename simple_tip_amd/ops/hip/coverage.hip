@@ -98,18 +98,8 @@ __global__ void popcount_kernel(
 // 64-bit key whose unsigned order is that order: the high word is the
 // float's bits made monotone, the low word is ~column. Key 0 would need the
 // bit pattern 0xffffffff, a NaN, and NaNs are canonicalised to the top, so 0
-// marks an empty slot below every real entry, -inf included.
-TIP_DEV unsigned long long tknc_key(float v, int c) {
-  unsigned int u = __float_as_uint(v);
-  if (v != v)
-    u = 0xffffffffu;  // NaN, either sign: above +inf
-  else if (v == 0.f)
-    u = 0x80000000u;  // -0.0 ranks with +0.0
-  else
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (unsigned int)~c;
-}
-
+// marks an empty slot below every real entry, -inf included. The key is
+// tknc_key in tip_common.h, shared with coverage_suite.hip.
 __global__ void tknc_kernel(
     const float* __restrict__ layer,  // [rows, K]
     int rows, int K, int k, int bit_offset, int W,

@@ -52,3 +52,18 @@ TIP_DEV uint32_t mix32(uint32_t x) {
   x ^= x >> 16;
   return x;
 }
+
+// TKNC sort key (coverage.hip, coverage_suite.hip): the unsigned order of the
+// keys is descending value with NaN greatest and -0.0 == 0.0, then ascending
+// column. The high word is the float's bits made monotone, the low word is
+// ~column; 0 is no key of a real entry and marks an empty slot.
+TIP_DEV unsigned long long tknc_key(float v, int c) {
+  unsigned int u = __float_as_uint(v);
+  if (v != v)
+    u = 0xffffffffu;  // NaN, either sign: above +inf
+  else if (v == 0.f)
+    u = 0x80000000u;  // -0.0 ranks with +0.0
+  else
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned int)~c;
+}

@@ -436,6 +436,103 @@ def tknc_profile(layer_acts: List[torch.Tensor], k: int) -> torch.Tensor:
     return words
 
 
+#: device envelope of the fused coverage suite (coverage_suite.hip)
+COVERAGE_SUITE_MAX_LAYERS = 8
+COVERAGE_SUITE_MAX_FAMILY = 4
+COVERAGE_SUITE_MAX_SECTIONS = 16
+COVERAGE_SUITE_MAX_TOPK = 4
+
+
+def coverage_suite_chunk() -> int:
+    """Neurons of the concatenated axis one block of the suite kernel owns."""
+    return _ext.coverage_suite_chunk()
+
+
+def _suite_table(t, ndim, k, name, dev):
+    """``t`` as an fp32 table on ``dev`` whose last axis is the K neurons;
+    None (or no rows) becomes an empty tensor."""
+    if t is None or t.shape[0] == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    if t.dim() != ndim or t.shape[-1] != k:
+        raise ValueError(
+            f"{name} must have width K={k} (got shape {tuple(t.shape)})"
+        )
+    return t.to(dev).float().contiguous()
+
+
+def coverage_suite(
+    layers,
+    nac_thresholds=(),
+    upper_bounds=None,
+    nbc_lower=None,
+    nbc_upper=None,
+    kmnc_mins=None,
+    kmnc_maxs=None,
+    kmnc_sections=(),
+    tknc_ks=(),
+):
+    from . import fallback
+
+    cap = COVERAGE_SUITE_MAX_FAMILY
+    layers = list(layers)
+    if not 1 <= len(layers) <= COVERAGE_SUITE_MAX_LAYERS:
+        raise ValueError(
+            f"coverage_suite on GPU takes 1..{COVERAGE_SUITE_MAX_LAYERS} "
+            f"layers (got {len(layers)})"
+        )
+    if any(l.dim() != 2 for l in layers):
+        raise ValueError("layers must be [N, K_l]")
+    n = layers[0].shape[0]
+    if any(l.shape[0] != n for l in layers):
+        raise ValueError("all layers must share N")
+    dev = layers[0].device
+    k = sum(l.shape[1] for l in layers)
+    nac_thresholds = tuple(float(t) for t in nac_thresholds)
+    kmnc_sections = tuple(int(v) for v in kmnc_sections)
+    tknc_ks = tuple(int(v) for v in tknc_ks)
+    if any(not 1 <= v <= COVERAGE_SUITE_MAX_SECTIONS for v in kmnc_sections):
+        raise ValueError(
+            f"kmnc_sections must lie in 1..{COVERAGE_SUITE_MAX_SECTIONS}"
+        )
+    if any(not 1 <= v <= COVERAGE_SUITE_MAX_TOPK for v in tknc_ks):
+        raise ValueError(f"tknc_ks must lie in 1..{COVERAGE_SUITE_MAX_TOPK}")
+    if (nbc_lower is None) != (nbc_upper is None) or (
+        nbc_lower is not None and nbc_lower.shape != nbc_upper.shape
+    ):
+        raise ValueError("nbc_lower and nbc_upper must have the same shape")
+    if kmnc_sections and (kmnc_mins is None or kmnc_maxs is None):
+        raise ValueError("kmnc_sections needs kmnc_mins and kmnc_maxs")
+    upper = _suite_table(upper_bounds, 2, k, "upper_bounds", dev)
+    lower_b = _suite_table(nbc_lower, 2, k, "nbc_lower", dev)
+    upper_b = _suite_table(nbc_upper, 2, k, "nbc_upper", dev)
+    mins = _suite_table(kmnc_mins if kmnc_sections else None, 1, k, "kmnc_mins", dev)
+    maxs = _suite_table(kmnc_maxs if kmnc_sections else None, 1, k, "kmnc_maxs", dev)
+    counts = {
+        "nac": len(nac_thresholds),
+        "snac": upper.shape[0] if upper.dim() == 2 else 0,
+        "nbc": lower_b.shape[0] if lower_b.dim() == 2 else 0,
+        "kmnc": len(kmnc_sections),
+        "tknc": len(tknc_ks),
+    }
+    for fam, c in counts.items():
+        if c > cap:
+            raise ValueError(
+                f"coverage_suite on GPU takes at most {cap} {fam} profiles "
+                f"per call (got {c})"
+            )
+    flat = _ext.coverage_suite(
+        [l.float().contiguous() for l in layers],
+        list(nac_thresholds), upper, lower_b, upper_b, mins, maxs,
+        list(kmnc_sections), list(tknc_ks),
+    )
+    scores = flat[-1]
+    out, at = {}, 0
+    for fam in fallback.COVERAGE_SUITE_FAMILIES:
+        out[fam] = [(flat[at + i], scores[at + i]) for i in range(counts[fam])]
+        at += counts[fam]
+    return out
+
+
 def bucketize_profile(values: torch.Tensor, thresholds: torch.Tensor) -> torch.Tensor:
     return _ext.bucketize(
         values.double().contiguous(),
