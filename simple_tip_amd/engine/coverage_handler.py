@@ -18,7 +18,7 @@ from ..core.bitmap import BitProfile
 from ..core.neuron_coverage import (
     KMNC, NAC, NBC, SNAC, TKNC, CoverageMethod, CoverageSuite,
 )
-from ..core.prioritizers import cam
+from ..core.prioritizers import cam, cam_many
 from ..core.timer import DeviceTimer
 from .model_handler import BaseModel, iter_batches
 
@@ -44,6 +44,15 @@ class CoverageWorker:
     path no metric could have been computed alone for less, so no table
     ever understates a metric's cost (the slots therefore do not add up to
     the wall time). ``pred`` is charged as in the per-metric mode.
+
+    ``cam_mode="batched"`` orders all 12 metrics with one
+    :func:`~simple_tip_amd.core.prioritizers.cam_many` call (on the GPU one
+    persistent launch, a team of blocks per metric) instead of one ``cam``
+    call per metric (``"per_metric"``, the default); the orders are
+    identical. ``TIP_CAM_MODE`` overrides the argument. Time accounting
+    follows the same rule: every metric's ``cam`` slot is charged the WHOLE
+    batched call, so no table understates a metric's cost and the slots do
+    not add up to the wall time.
     """
 
     def __init__(
@@ -52,6 +61,7 @@ class CoverageWorker:
         training_set,
         dist_shard: bool = False,
         nc_mode: str = "per_metric",
+        cam_mode: str = "per_metric",
     ):
         from ..parallel.dist import get_world_size, shard_slice
         from .aggregate_statistics import AggregateStatisticsCollector
@@ -62,6 +72,12 @@ class CoverageWorker:
                 f"nc_mode must be 'per_metric' or 'fused', got {nc_mode!r}"
             )
         self.nc_mode = nc_mode
+        cam_mode = os.environ.get("TIP_CAM_MODE", cam_mode)
+        if cam_mode not in ("per_metric", "batched"):
+            raise ValueError(
+                f"cam_mode must be 'per_metric' or 'batched', got {cam_mode!r}"
+            )
+        self.cam_mode = cam_mode
         self._suite = None
         self.base_model = base_model
         self.dist_shard = bool(dist_shard) and get_world_size() > 1
@@ -179,6 +195,7 @@ class CoverageWorker:
 
         all_scores: Dict[str, np.ndarray] = {}
         cam_orders: Dict[str, List[int]] = {}
+        assembled: Dict[str, Tuple[torch.Tensor, BitProfile]] = {}
         for metric_id in self.metrics.keys():
             scores = torch.cat(scores_parts[metric_id])
             profile = BitProfile.cat(profile_parts[metric_id])
@@ -187,6 +204,9 @@ class CoverageWorker:
                     scores, profile, n_total, my_slice
                 )
             all_scores[metric_id] = scores.cpu().numpy()
+            if self.cam_mode == "batched":
+                assembled[metric_id] = (scores.float(), profile)
+                continue
             logger.info("Calculating CAM for %s (%s)", metric_id, test_dataset_id)
             timer = DeviceTimer()
             with timer:
@@ -194,6 +214,21 @@ class CoverageWorker:
             times[metric_id].append(timer.get())
             self._cam_sanity_check(order, all_scores[metric_id])
             cam_orders[metric_id] = order
+        if self.cam_mode == "batched":
+            logger.info(
+                "Calculating CAM for %d metrics in one call (%s)",
+                len(assembled), test_dataset_id,
+            )
+            timer = DeviceTimer()
+            with timer:
+                orders = cam_many(
+                    [s for s, _ in assembled.values()],
+                    [p for _, p in assembled.values()],
+                )
+            for metric_id, order in zip(assembled.keys(), orders):
+                times[metric_id].append(timer.get())  # the whole call, each
+                self._cam_sanity_check(order, all_scores[metric_id])
+                cam_orders[metric_id] = order
         return times, all_scores, cam_orders
 
     @staticmethod

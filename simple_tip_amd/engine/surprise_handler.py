@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from ..config import NUM_SC_BUCKETS
-from ..core.prioritizers import cam
+from ..core.prioritizers import cam, cam_many
 from ..core.surprise import DSA, LSA, MDSA, MLSA, MultiModalSA, SurpriseCoverageMapper
 from ..core.timer import DeviceTimer
 from .model_handler import BaseModel
@@ -49,6 +49,7 @@ class SurpriseHandler:
         predict_batch: int = 512,
         dist_shard: bool = False,
         modal_sa_mode: str = "per_mode",
+        cam_mode: str = "per_metric",
     ):
         from ..parallel.dist import get_world_size
 
@@ -62,6 +63,18 @@ class SurpriseHandler:
                 f"modal_sa_mode must be 'per_mode' or 'fused', got {modal_sa_mode!r}"
             )
         self.modal_sa_mode = modal_sa_mode
+        # "batched": the surprise-coverage profiles of every (SA, dataset)
+        # pair are ordered by one cam_many call (on the GPU one persistent
+        # launch, a team of blocks per pair) instead of one cam call each
+        # ("per_metric", the default); the orders are identical. Every
+        # pair's cam time slot is then charged the WHOLE call, the rule of
+        # CoverageWorker's fused modes. TIP_CAM_MODE overrides.
+        cam_mode = os.environ.get("TIP_CAM_MODE", cam_mode)
+        if cam_mode not in ("per_metric", "batched"):
+            raise ValueError(
+                f"cam_mode must be 'per_metric' or 'batched', got {cam_mode!r}"
+            )
+        self.cam_mode = cam_mode
         self.sa_layers = list(sa_layers)
         # dist_shard: shard AT-extraction and SA scoring over the test-input
         # axis across ranks (DP per SURVEY §2.4); train ATs are extracted
@@ -143,18 +156,42 @@ class SurpriseHandler:
                         sa_vals = allgather_rows(sa_vals.contiguous(), n)
                 res[sa_name][ds_name] = (sa_vals, [setup_time, pred_time, sa_timer.get()])
 
+        if self.cam_mode == "batched":
+            return self._cam_batched(res, datasets)
         for sa_name in self.TESTED_SA.keys():
             for ds_name in datasets.keys():
                 sa_vals, times = res[sa_name][ds_name]
                 cam_timer = DeviceTimer()
                 with cam_timer:
-                    vals_t = torch.as_tensor(sa_vals)
-                    finite = vals_t[torch.isfinite(vals_t)]
-                    upper = float(finite.max()) if finite.numel() else 1.0
-                    mapper = SurpriseCoverageMapper(NUM_SC_BUCKETS, upper)
-                    profiles = mapper.get_coverage_profile(vals_t)
+                    vals_t, profiles = self._coverage_profile(sa_vals)
                     cam_order = np.array(list(cam(vals_t.float(), profiles)))
                 times = times + [cam_timer.get()]
                 sa_np = vals_t.double().cpu().numpy()
                 res[sa_name][ds_name] = (sa_np, cam_order, times)
+        return res
+
+    @staticmethod
+    def _coverage_profile(sa_vals):
+        """(values as a tensor, their surprise-coverage profile) with the
+        dynamic upper bound: the largest finite value."""
+        vals_t = torch.as_tensor(sa_vals)
+        finite = vals_t[torch.isfinite(vals_t)]
+        upper = float(finite.max()) if finite.numel() else 1.0
+        mapper = SurpriseCoverageMapper(NUM_SC_BUCKETS, upper)
+        return vals_t, mapper.get_coverage_profile(vals_t)
+
+    def _cam_batched(self, res, datasets):
+        """The final loop of ``evaluate_all`` with every (SA, dataset) pair
+        ordered by one ``cam_many`` call."""
+        keys = [(sa, ds) for sa in self.TESTED_SA.keys() for ds in datasets.keys()]
+        cam_timer = DeviceTimer()
+        with cam_timer:
+            pairs = [self._coverage_profile(res[sa][ds][0]) for sa, ds in keys]
+            orders = cam_many(
+                [v.float() for v, _ in pairs], [p for _, p in pairs]
+            )
+        for (sa, ds), (vals_t, _), order in zip(keys, pairs, orders):
+            times = res[sa][ds][1] + [cam_timer.get()]  # the whole call, each
+            sa_np = vals_t.double().cpu().numpy()
+            res[sa][ds] = (sa_np, np.array(order), times)
         return res

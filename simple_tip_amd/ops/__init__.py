@@ -12,7 +12,7 @@ the fallback.
 """
 
 import os
-from typing import Dict, List, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
@@ -86,6 +86,48 @@ def ctm_order(scores: torch.Tensor) -> torch.Tensor:
 
 def cam_order(scores: torch.Tensor, words: torch.Tensor, nbits: int) -> torch.Tensor:
     return _route(words).cam_order(scores, words, nbits)
+
+
+def cam_order_many(
+    scores: Sequence[torch.Tensor],
+    words: Sequence[torch.Tensor],
+    nbits: Sequence[int],
+) -> List[torch.Tensor]:
+    """The CAM orders of P independent problems.
+
+    ``scores[p]`` is [N_p], ``words[p]`` a contiguous int64 [N_p, W_p]
+    packed profile with ``W_p == ceil(nbits[p] / 64)``; rows, widths and
+    ``nbits`` may differ freely between the problems. ``out[p]`` equals
+    ``cam_order(scores[p], words[p], nbits[p])`` element for element, for
+    every input: greedy max-cover, ties to the lowest row, bits past
+    ``nbits`` ignored, the loop stops when no row adds coverage, leftovers
+    by descending score, stable. ``P == 0`` returns ``[]`` and a problem
+    with 0 rows an empty order.
+
+    On GPU tensors one persistent launch serves up to
+    :func:`cam_many_max_problems` problems, each on its own team of blocks,
+    reading the profiles where they lie; more problems are split into
+    consecutive launches. All arithmetic is integer: a problem's order does
+    not depend on the other problems of the call, on their order or on how
+    the grid was divided. Tensors on different devices, ``words`` that is
+    not contiguous int64 2-D, ``W_p != ceil(nbits_p / 64)`` or a ``scores``
+    of another length raise ValueError, the call never falls back. A team
+    whose bounded barrier wait runs out raises RuntimeError naming the
+    problem; a partial order is never returned.
+    """
+    words = list(words)
+    if not words:
+        return fallback.cam_order_many(scores, words, nbits)
+    return _route(words[0]).cam_order_many(scores, words, nbits)
+
+
+def cam_many_max_problems() -> int:
+    """Problems one launch of the GPU batched-CAM kernel takes; needs the
+    HIP extension."""
+    ext = _load_ext()
+    if ext is None:
+        raise RuntimeError(f"HIP extension not importable: {_EXT_ERR!r}")
+    return ext.cam_many_max_problems()
 
 
 # --- pairwise-distance family ----------------------------------------------

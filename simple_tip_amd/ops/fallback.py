@@ -13,7 +13,7 @@ the reference's row-major ``(N, K, S)`` flattening
 (reference: src/core/neuron_coverage.py:82-94, 118-128).
 """
 
-from typing import Dict, NamedTuple, Tuple
+from typing import Dict, List, NamedTuple, Tuple
 
 import numpy as np
 import torch
@@ -113,6 +113,20 @@ def cam_order(scores: torch.Tensor, words: torch.Tensor, nbits: int) -> torch.Te
         left = left[np.argsort(-s[left], kind="stable")]
         order.extend(int(i) for i in left)
     return torch.tensor(order, dtype=torch.long, device=scores.device)
+
+
+def cam_order_many(scores, words, nbits) -> List[torch.Tensor]:
+    """:func:`cam_order` of every problem ``(scores[p], words[p], nbits[p])``."""
+    scores, words, nbits = list(scores), list(words), list(nbits)
+    if not len(scores) == len(words) == len(nbits):
+        raise ValueError("scores, words and nbits must have one entry per problem")
+    # (a problem without rows has the empty order; cam_order wants a row)
+    return [
+        cam_order(s, w, int(b))
+        if s.shape[0]
+        else torch.empty(0, dtype=torch.long, device=s.device)
+        for s, w, b in zip(scores, words, nbits)
+    ]
 
 
 def _popcount_np(w: np.ndarray) -> np.ndarray:

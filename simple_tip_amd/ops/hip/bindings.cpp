@@ -9,9 +9,11 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <vector>
 
+#include "cam_many.h"
 #include "coverage_suite.h"
 
 // launchers defined in the .hip translation units
@@ -600,6 +602,131 @@ torch::Tensor cam_greedy(torch::Tensor words, int64_t nbits) {
   return order_dev.narrow(0, 0, n).cpu();
 }
 
+// Batched CAM (cam_many.hip): the greedy loops of 1..CAM_MANY_MAX_PROBLEMS
+// problems in one persistent launch, one team of blocks per problem. The
+// profile matrices are read where they lie. One device-to-host copy brings
+// every pick count and status word; the picked prefixes stay on the device
+// and are returned as views of one buffer. A problem whose bounded wait ran
+// out raises, no partial order is returned.
+// Measurement switch (scripts/perf_cam_many.py): no pick publishes a list, so
+// every sweep recounts against the whole mask. Orders do not change.
+bool g_cam_many_force_full = false;
+void cam_many_force_full(bool on) { g_cam_many_force_full = on; }
+
+std::vector<torch::Tensor> cam_greedy_many(std::vector<torch::Tensor> words,
+                                           std::vector<int64_t> nbits) {
+  const int P = (int)words.size();
+  TORCH_CHECK(P >= 1 && P <= CAM_MANY_MAX_PROBLEMS && (int)nbits.size() == P,
+              "cam_greedy_many takes 1..", CAM_MANY_MAX_PROBLEMS,
+              " problems per call");
+  std::vector<int64_t> rows(P), Ws(P);
+  for (int p = 0; p < P; ++p) {
+    const auto& w = words[p];
+    TORCH_CHECK(w.is_cuda() && w.dtype() == torch::kInt64 && w.dim() == 2 &&
+                    w.is_contiguous() && w.device() == words[0].device(),
+                "cam_greedy_many: words[", p,
+                "] must be a contiguous int64 [N, W] tensor on one device");
+    rows[p] = w.size(0);
+    Ws[p] = w.size(1);
+    // the barrier counter (2 * rows * team) and the gains (W * 64) are ints
+    TORCH_CHECK(rows[p] >= 1 && rows[p] < (1 << 23) && Ws[p] >= 1 &&
+                    Ws[p] < (1 << 24) && Ws[p] == (nbits[p] + 63) / 64,
+                "cam_greedy_many: problem ", p, " is outside the envelope");
+  }
+  const int grid = cam_many_grid();
+  TORCH_CHECK(grid >= P, "cam_greedy_many: ", P, " problems need ", P,
+              " CUs, the device reports ", grid);
+  const std::vector<int> team = cam_many_teams(rows, Ws, grid);
+
+  int64_t n_rows = 0, n_words = 0, n_list = 0, n_team = 0;
+  std::vector<int> list_cap(P);
+  for (int p = 0; p < P; ++p) {
+    list_cap[p] = g_cam_many_force_full
+                      ? 0
+                      : (int)std::min<int64_t>(Ws[p] / CAM_MANY_INCR_DIV,
+                                               CAM_MANY_LIST_CAP);
+    n_rows += rows[p];
+    n_words += Ws[p];
+    n_list += 2 * list_cap[p];
+    n_team += team[p];
+  }
+  auto o64 = words[0].options();
+  auto o32 = o64.dtype(torch::kInt32);
+  // [counts P | status P | orders]; only the head is zeroed and read back
+  auto res = torch::empty({2 * P + n_rows}, o64);
+  res.narrow(0, 0, 2 * P).zero_();
+  auto ws64 = torch::empty({n_words + n_list}, o64);        // masks, lists
+  auto ws32 = torch::empty({n_rows + 2 * n_team}, o32);     // gains, maxima
+  auto sync = torch::zeros({(int64_t)P * CAM_MANY_SYNC_WORDS}, o32);
+
+  std::vector<CamManyDesc> table(P);
+  auto* res_p = reinterpret_cast<long long*>(res.data_ptr<int64_t>());
+  auto* w64 = reinterpret_cast<unsigned long long*>(ws64.data_ptr<int64_t>());
+  int* w32 = ws32.data_ptr<int>();
+  int64_t at_row = 0, at_word = 0, at_list = 0, at_team = 0;
+  for (int p = 0; p < P; ++p) {
+    CamManyDesc& d = table[p];
+    const int tail = (int)(nbits[p] % 64);
+    d.words = reinterpret_cast<const unsigned long long*>(
+        words[p].data_ptr<int64_t>());
+    d.uncovered = w64 + at_word;
+    d.list = w64 + n_words + at_list;
+    d.gain = w32 + at_row;
+    d.part_val = w32 + n_rows + at_team;
+    d.part_idx = w32 + n_rows + n_team + at_team;
+    d.order = res_p + 2 * P + at_row;
+    d.count = res_p + p;
+    d.status = res_p + P + p;
+    d.sync = sync.data_ptr<int>() + (int64_t)p * CAM_MANY_SYNC_WORDS;
+    d.tail_mask = tail ? ((1ull << tail) - 1) : ~0ull;
+    d.rows = (int)rows[p];
+    d.W = (int)Ws[p];
+    d.first_block = (int)at_team;
+    d.team = team[p];
+    d.list_cap = list_cap[p];
+    d.wide = Ws[p] >= CAM_MANY_WIDE_WORDS;
+    at_row += rows[p];
+    at_word += Ws[p];
+    at_list += 2 * list_cap[p];
+    at_team += team[p];
+  }
+  TORCH_CHECK(at_team <= grid, "cam_greedy_many: team plan exceeds the grid");
+  auto table_dev =
+      torch::from_blob(table.data(), {(int64_t)(P * sizeof(CamManyDesc))},
+                       torch::dtype(torch::kUInt8))
+          .to(words[0].device());
+  launch_cam_many(reinterpret_cast<const CamManyDesc*>(
+                      table_dev.data_ptr<uint8_t>()),
+                  P, grid, cur_stream());
+  const auto head = res.narrow(0, 0, 2 * P).cpu();  // waits for the launch
+  const int64_t* h = head.data_ptr<int64_t>();
+  for (int p = 0; p < P; ++p)
+    TORCH_CHECK(h[P + p] == 0, "cam_greedy_many: problem ", p, " (", rows[p],
+                " x ", Ws[p], " words, team of ", team[p],
+                " blocks) ran into the bound of a team-barrier wait; no "
+                "order is returned");
+  std::vector<torch::Tensor> out(P);
+  at_row = 0;
+  for (int p = 0; p < P; ++p) {
+    out[p] = res.narrow(0, 2 * P + at_row, h[p]);
+    at_row += rows[p];
+  }
+  return out;
+}
+
+std::vector<int64_t> cam_many_plan(std::vector<int64_t> rows,
+                                   std::vector<int64_t> W, int64_t grid) {
+  TORCH_CHECK(rows.size() == W.size() && (int64_t)rows.size() <= grid);
+  const std::vector<int> team = cam_many_teams(rows, W, (int)grid);
+  return std::vector<int64_t>(team.begin(), team.end());
+}
+
+int64_t cam_many_max_problems() { return CAM_MANY_MAX_PROBLEMS; }
+int64_t cam_many_wide_words() { return CAM_MANY_WIDE_WORDS; }
+int64_t cam_many_incr_div() { return CAM_MANY_INCR_DIV; }
+int64_t cam_many_list_cap() { return CAM_MANY_LIST_CAP; }
+int64_t cam_many_team_cap() { return CAM_MANY_TEAM_CAP; }
+
 // All-pairs Levenshtein distance matrix (CPU, threaded) for the text
 // corruptor's autocorrect dictionary (the reference uses the
 // polyleven pip package on a thread pool, text_corruptor.py:282-309).
@@ -1131,6 +1258,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("coverage_suite", &coverage_suite);
   m.def("coverage_suite_chunk", &coverage_suite_chunk_py);
   m.def("cam_greedy", &cam_greedy);
+  m.def("cam_greedy_many", &cam_greedy_many);
+  m.def("cam_many_force_full", &cam_many_force_full);
+  m.def("cam_many_plan", &cam_many_plan);
+  m.def("cam_many_max_problems", &cam_many_max_problems);
+  m.def("cam_many_wide_words", &cam_many_wide_words);
+  m.def("cam_many_incr_div", &cam_many_incr_div);
+  m.def("cam_many_list_cap", &cam_many_list_cap);
+  m.def("cam_many_team_cap", &cam_many_team_cap);
   m.def("softmax_scores", &softmax_scores);
   m.def("levenshtein_matrix", &levenshtein_matrix);
   m.def("mfma_probe", &mfma_probe);

@@ -4,7 +4,7 @@ Presents the same API as ops/fallback.py; ops/__init__.py routes CUDA
 tensors here. Import fails (propagated by the dispatcher as a loud error)
 when the extension .so is missing."""
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
@@ -34,8 +34,9 @@ def ctm_order(scores: torch.Tensor) -> torch.Tensor:
     return torch.argsort(scores, descending=True, stable=True)
 
 
-def cam_order(scores: torch.Tensor, words: torch.Tensor, nbits: int) -> torch.Tensor:
-    picked = _ext.cam_greedy(words.contiguous(), nbits).to(scores.device)
+def _cam_with_leftovers(scores: torch.Tensor, picked: torch.Tensor) -> torch.Tensor:
+    """``picked`` (the rows that added coverage) followed by the other rows
+    by descending score, stable."""
     n = scores.shape[0]
     mask = torch.ones(n, dtype=torch.bool, device=scores.device)
     if picked.numel():
@@ -47,6 +48,89 @@ def cam_order(scores: torch.Tensor, words: torch.Tensor, nbits: int) -> torch.Te
         ]
         return torch.cat([picked, order_left])
     return picked
+
+
+def cam_order(scores: torch.Tensor, words: torch.Tensor, nbits: int) -> torch.Tensor:
+    picked = _ext.cam_greedy(words.contiguous(), nbits).to(scores.device)
+    return _cam_with_leftovers(scores, picked)
+
+
+def cam_many_max_problems() -> int:
+    """Problems one launch of the batched CAM kernel takes."""
+    return _ext.cam_many_max_problems()
+
+
+#: constants of cam_many.hip: full sweeps give a row to a wave from
+#: CAM_MANY_WIDE_WORDS words on; a pick whose ``newly`` mask has L non-zero
+#: words updates the gains incrementally when L * CAM_MANY_INCR_DIV <= W and
+#: L <= CAM_MANY_LIST_CAP; a team has at most CAM_MANY_TEAM_CAP blocks
+CAM_MANY_WIDE_WORDS = _ext.cam_many_wide_words()
+CAM_MANY_INCR_DIV = _ext.cam_many_incr_div()
+CAM_MANY_LIST_CAP = _ext.cam_many_list_cap()
+CAM_MANY_TEAM_CAP = _ext.cam_many_team_cap()
+
+
+def cam_many_force_full(on: bool) -> None:
+    """Measurement switch: with ``on`` the batched kernel recounts every row
+    after every pick instead of updating the gains from the pick's list.
+    Orders do not change."""
+    _ext.cam_many_force_full(bool(on))
+
+
+def cam_many_plan(rows: Sequence[int], widths: Sequence[int], grid: int) -> List[int]:
+    """Blocks per problem of one launch on a grid of ``grid`` blocks."""
+    return _ext.cam_many_plan([int(r) for r in rows], [int(w) for w in widths], int(grid))
+
+
+def cam_order_many(scores, words, nbits) -> List[torch.Tensor]:
+    scores, words = list(scores), list(words)
+    nbits = [int(b) for b in nbits]
+    if not len(scores) == len(words) == len(nbits):
+        raise ValueError("scores, words and nbits must have one entry per problem")
+    if not words:
+        return []
+    dev = words[0].device
+    for p, (s, w, b) in enumerate(zip(scores, words, nbits)):
+        if s.device != dev or w.device != dev:
+            raise ValueError(
+                f"cam_order_many: problem {p} is on {s.device} / {w.device}, "
+                f"problem 0 on {dev}; all tensors must share one device"
+            )
+        if w.dtype != torch.int64 or w.dim() != 2 or not w.is_contiguous():
+            raise ValueError(
+                f"cam_order_many: words[{p}] must be a contiguous int64 "
+                f"[N, W] tensor (got {w.dtype}, shape {tuple(w.shape)})"
+            )
+        if b < 0 or w.shape[1] != (b + 63) // 64:
+            raise ValueError(
+                f"cam_order_many: words[{p}] has {w.shape[1]} words per row, "
+                f"nbits={b} needs {(b + 63) // 64}"
+            )
+        if s.dim() != 1 or s.shape[0] != w.shape[0]:
+            raise ValueError(
+                f"cam_order_many: scores[{p}] has shape {tuple(s.shape)}, "
+                f"words[{p}] has {w.shape[0]} rows"
+            )
+        if w.shape[0] >= 1 << 23 or w.shape[1] >= 1 << 24:
+            raise ValueError(
+                f"cam_order_many on GPU takes fewer than 2^23 rows of fewer "
+                f"than 2^24 words (problem {p}: {tuple(w.shape)})"
+            )
+    # a problem without rows or without bits picks nothing: no team for it
+    live = [p for p, w in enumerate(words) if w.shape[0] and w.shape[1]]
+    picked = {}
+    step = cam_many_max_problems()
+    for lo in range(0, len(live), step):
+        chunk = live[lo : lo + step]
+        outs = _ext.cam_greedy_many(
+            [words[p] for p in chunk], [nbits[p] for p in chunk]
+        )
+        picked.update(zip(chunk, outs))
+    empty = torch.empty(0, dtype=torch.int64, device=dev)
+    return [
+        _cam_with_leftovers(scores[p], picked.get(p, empty))
+        for p in range(len(words))
+    ]
 
 
 def pairwise_sqdist(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
