@@ -13,8 +13,9 @@
 //
 // Layout/geometry:
 // - activations: NHWC bf16; LDS image [(H+2) x (W+2) x C] with zeroed halo,
-//   16-byte units XOR-swizzled (u ^= (u>>4)&7) so the per-tap
-//   ds_read_b128 gathers are bank-conflict-free for C in {16, 32, 64}.
+//   in 16-byte units, packed unit-row-major (the XOR swizzle family below
+//   lost its sweep and is off), except the 8x8x64 image, whose rows are
+//   padded by two units against bank conflicts (see Img).
 // - MFMA: v_mfma_f32_16x16x32_bf16. M = 16 consecutive output pixels
 //   (row-major in the plane), N = 16 output channels, K = 32 consecutive
 //   (tap, channel) pairs of the 3x3xC patch (zero-padded to a multiple
@@ -27,10 +28,10 @@
 //   weight fragment goes in as the FIRST operand and the pixel fragment as
 //   the second: D = W^T P^T, col = lane&15 = pixel, row = (lane>>4)*4 + reg
 //   = cout, which gives a lane 4 consecutive couts of one pixel to store.
-//   (The small-plane path of conv3x3 keeps pixel-first operands; see there.)
 //   (The layout is verified at runtime by the mfma_probe test kernel, and
 //   that the swap changes no fp32 bit by test_gpu_resnet_conv_epilogue.)
-// - one workgroup = one image; 4 waves split the plane's 16-pixel tiles.
+// - one workgroup = one image; 4 waves split the plane's 16-pixel tiles
+//   (the 8x8x64 planes: 2 cout tiles x 2 pixel tiles per wave).
 
 #pragma once
 
@@ -73,6 +74,28 @@ TIP_DEV int swz(int u) {
 #define TIP_HALFPLANE 0
 #endif
 
+// Strides of the 8x8x64 image, in 16-B units (packed: 8 and 80). A pixel
+// tile of the 8x8 plane is two rows of 8, and a ds_read_b128 lane group
+// holds x = 0..3 of one row and x = 4..7 of the other, for each of two
+// k-groups. Packed, the pixel stride (128 B) and the row stride (1280 B = 0
+// mod 256) put the 8 lanes of a k-group on two 16-B bank slots: 4-way. A row
+// stride of 82 (1312 B) moves the second row to other slots: 2-way, for 288
+// bytes per image. Enumerated over every tap, k-step and tile: 864 extra
+// LDS cycles per conv packed, 288 at (8, 82), 0 at (10, 112); the last
+// costs stage 2 a workgroup per CU and measured no faster in stage 3 once
+// the tiles are dealt 2 x 2 (profiles/r14_small_plane_weights.md). Every
+// fragment address stays base + compile-time constant: no per-read XOR.
+#ifndef TIP_IMG64_PS
+#define TIP_IMG64_PS 8
+#endif
+#ifndef TIP_IMG64_RS
+#define TIP_IMG64_RS 82
+#endif
+// Cout tiles per wave in conv3x3's small-plane path (1, 2 or 4).
+#ifndef TIP_SP_NC
+#define TIP_SP_NC 2
+#endif
+
 template <int H, int W, int C>
 struct Img {
   static constexpr int UPP = C / 8;  // 16-B units per pixel
@@ -85,10 +108,19 @@ struct Img {
     return h * PLANE + y * RS1 + x;
   }
 #else
-  static constexpr int UNITS = (H + 2) * (W + 2) * UPP;
-  static constexpr int XSTEP = UPP;
+  // The layout is a property of the geometry: padded strides for the
+  // 8x8x64 image, packed unit-row-major for every other.
+  static constexpr bool PADDED = (H == 8 && W == 8 && C == 64);
+  static constexpr int PS = PADDED ? TIP_IMG64_PS : UPP;  // units per pixel step
+  static constexpr int RS = PADDED ? TIP_IMG64_RS : (W + 2) * UPP;  // per row
+  static_assert(PS >= UPP && RS >= (W + 2) * PS, "strides overlap");
+  static constexpr int UNITS = (H + 1) * RS + (W + 2) * PS;
+  static constexpr int XSTEP = PS;
   static TIP_DEV int unit(int y, int x, int h) {
-    return (y * (W + 2) + x) * UPP + h;
+    // the packed images keep the expression their code was tuned with: the
+    // strided form of the same value compiles stage 1 to 3 % slower code
+    if constexpr (!PADDED) return (y * (W + 2) + x) * UPP + h;
+    return y * RS + x * PS + h;
   }
 #endif
 };
@@ -131,7 +163,7 @@ TIP_DEV void stage_plane(short* lds, const short* __restrict__ gsrc) {
   load_interior<H, W, C>(lds, gsrc);
 }
 
-// Epilogue helpers. The convs (all but conv3x3's small-plane path) issue the
+// Epilogue helpers. The convs issue the
 // MFMA with the WEIGHT fragment as the first operand and the PIXEL fragment
 // as the second, so D comes out transposed: lane = pixel l&15, registers =
 // couts (l>>4)*4 + reg. A lane then owns 4 consecutive couts of one pixel —
@@ -250,79 +282,59 @@ TIP_DEV void conv3x3(
     }
   };
 
-  // Small-plane specialization (PIX_TILES <= 4, i.e. the 8x8 stage): each
-  // wave owns at most ONE pixel tile, so the generic path's dual-PIXEL
-  // MFMA chains collapse to a single dependent chain (measured 24% slower
-  // per FLOP than the 32x32 stage). Interleave TWO COUT tiles instead:
-  // the pixel fragment is shared, the weight fragments load from L2 per
-  // k-step (high occupancy here — 6 blocks/CU — hides the load latency the
-  // preload design was protecting the low-occupancy stages from).
-  // This path keeps the ORIGINAL operand roles (pixel fragment first, D
-  // col = lane&15 = cout, row = (lane>>4)*4 + reg = pixel) and the
-  // element-wise epilogue: it waits on the L2 weight loads, not on LDS, and
-  // with the swapped roles and the packed epilogue it measured 5.6 % slower
-  // in stage 3 and lost stage 2 its whole gain (sharing the fragment across
-  // all four cout tiles: no better); profiles/r09_conv_lds_traffic.md. The
-  // sums are the same either way, bit for bit.
-  if constexpr (PIX_TILES <= 4 && CTG == 2) {
-    const int pt = wid;
-    if (pt >= PIX_TILES) return;
-    const int apix = pt * 16 + j;
-    const int aoy = apix / OW, aox = apix - aoy * OW;
-    const int abase = In::unit(aoy * STRIDE, aox * STRIDE, 0);
-    for (int ct = 0; ct < COUT_TILES; ct += 2) {
-      const short* wp0 = wpack + ((int64_t)ct * KSTEPS) * 64 * 8 + lane * 8;
-      const short* wp1 = wp0 + (int64_t)KSTEPS * 64 * 8;
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f};
-      f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
+  // Small-plane specialization (4 pixel tiles x 4 cout tiles: the 8x8x64
+  // output planes). Dealing the PIXEL tiles to the waves, as the generic path
+  // does, makes every wave of the workgroup load the whole weight tensor:
+  // four fetches of each weight byte per image, which kept stage 3 waiting
+  // on vector memory (profiles/r14_small_plane_weights.md). Here a wave owns
+  // NC cout tiles x NP pixel tiles (NC * NP = 4). NC = 2 ships: each weight
+  // fragment is loaded by two waves of the workgroup instead of four, each
+  // pixel fragment read by two instead of one (as before), and a wave runs
+  // four independent MFMA chains. NC = 1 loads every weight byte once but
+  // doubles the ds_read_b128 count, which then binds: slower than the old
+  // dealing on the packed image, and only level with NC = 2 on a
+  // conflict-free one. The weight fragments are loaded per k-step (the
+  // unrolled loop lets the compiler issue them ahead); operand roles and
+  // epilogue are the generic path's. Each (pixel tile, cout tile)
+  // accumulator is one chain from zero over ks ascending, as everywhere.
+  if constexpr (PIX_TILES == 4 && COUT_TILES == 4) {
+    constexpr int NC = TIP_SP_NC, NP = 4 / NC;
+    static_assert(NC == 1 || NC == 2 || NC == 4, "NC divides the 4 cout tiles");
+    const int ct0 = (wid % (4 / NC)) * NC;
+    const int pt0 = (wid / (4 / NC)) * NP;
+    const short* wp = wpack + ((int64_t)ct0 * KSTEPS) * 64 * 8 + lane * 8;
+    TilePix p[NP];
+    int base[NP];
+    f32x4 acc[NC][NP];
 #pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        const int k0 = ks * 32 + g * 8;
-        short8 a;
-        if (k0 < K) {
-          const int tap = k0 / C;
-          const int ci = k0 & (C - 1);
-          const int dy = (tap * 11) >> 5;
-          const int dx = tap - dy * 3;
-          a = lds_read_unit(in_lds, abase + In::unit(dy, dx, ci >> 3));
-        } else {
-          a = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-        const short8 b0 =
-            *reinterpret_cast<const short8*>(wp0 + (int64_t)ks * 64 * 8);
-        const short8 b1 =
-            *reinterpret_cast<const short8*>(wp1 + (int64_t)ks * 64 * 8);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b1, acc1, 0, 0, 0);
-      }
+    for (int t = 0; t < NP; ++t) {
+      p[t] = tile_pix<OW>(pt0 + t, j);
+      base[t] = a_base(p[t]);
 #pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int cout = (ct + half) * 16 + j;
-        const float bs = bias[cout];
-        const f32x4& acc = half ? acc1 : acc0;
-        const int pix0 = pt * 16 + g * 4;
-        const int oy = pix0 / OW, ox = pix0 - oy * OW;
-        const int u0 = Out::unit(oy + 1, ox + 1, cout >> 3);
-        const int e = cout & 7;
+      for (int c = 0; c < NC; ++c) acc[c][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          float v = acc[reg] + bs;
-          if (RESID) {
-            const short* rimg = INPLACE ? out_lds : rlds;
-            const short* runit = rimg + swz(u0 + reg * Out::XSTEP) * 8;
-            v += __bfloat162float(reinterpret_cast<const bf16*>(runit)[e]);
-          }
-          v = fmaxf(v, 0.f);
-          const bf16 ov = __float2bfloat16(v);
-          if (TO_LDS) {
-            short* unit = out_lds + swz(u0 + reg * Out::XSTEP) * 8;
-            reinterpret_cast<bf16*>(unit)[e] = ov;
-          } else {
-            reinterpret_cast<bf16*>(gout)[(int64_t)(pix0 + reg) * COUT + cout] =
-                ov;
-          }
-        }
-      }
+    for (int ks = 0; ks < KSTEPS; ++ks) {
+      short8 b[NC], a[NP];
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        b[c] = *reinterpret_cast<const short8*>(
+            wp + ((int64_t)c * KSTEPS + ks) * 64 * 8);
+#pragma unroll
+      for (int t = 0; t < NP; ++t) a[t] = read_a(base[t], ks);
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int t = 0; t < NP; ++t)
+          acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              b[c], a[t], acc[c][t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const f32x4 bs = load_bias(ct0 + c);
+#pragma unroll
+      for (int t = 0; t < NP; ++t)
+        epilogue(pt0 + t, p[t], ct0 + c, acc[c][t], bs);
     }
     return;
   }

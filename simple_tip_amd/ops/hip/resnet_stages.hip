@@ -149,11 +149,13 @@ TIP_DEV void down_block_lds(const short* X, short* Hb, short* R,
 constexpr int kStage1Lds =
     (Img<32, 32, 16>::UNITS + 2 * Img<16, 16, 32>::UNITS) * 16;  // 78464
 constexpr int kStage2Lds =
-    (Img<16, 16, 32>::UNITS + 2 * Img<8, 8, 64>::UNITS) * 16;    // 46336
-constexpr int kStage3Lds = 2 * Img<8, 8, 64>::UNITS * 16;        // 25600
+    (Img<16, 16, 32>::UNITS + 2 * Img<8, 8, 64>::UNITS) * 16;    // 46912
+constexpr int kStage3Lds = 2 * Img<8, 8, 64>::UNITS * 16;        // 26176
 static_assert(2 * Img<16, 16, 32>::UNITS >= Img<32, 32, 16>::UNITS &&
               2 * Img<8, 8, 64>::UNITS >= Img<16, 16, 32>::UNITS,
               "second region must hold the stage's H image");
+static_assert(3 * kStage2Lds <= 160 * 1024 && 4 * kStage3Lds <= 160 * 1024,
+              "the padded 8x8x64 image must not cost a workgroup per CU");
 
 // Stage 1: fp32 input -> bf16, stem, 3 x res<32,32,16>, down<32,32,16>.
 // The 8-channel input image lives in the second region until the stem has
