@@ -170,6 +170,88 @@ def test_lsa_against_fp32(case):
     assert corr > 0.98
 
 
+WIDE_BAD = [5, 650]  # rows of the wide case given out-of-range predictions
+
+
+@functools.lru_cache(maxsize=None)
+def _run_wide():
+    """The skewed case with LSA(max_features=200), so that FusedPrioritizer
+    itself launches the wide (more than 64 features) whiten instantiation,
+    plus two predictions outside the fitted range. The LSA workspaces are
+    filled with NaN before the judged call."""
+    from simple_tip_amd.core.surprise import DSA, LSA, MultiModalSA
+    from simple_tip_amd.engine.serving import FusedPrioritizer
+    from test_gpu_lsa_oracles import NAN_BITS
+
+    dev = torch.device("cuda:0")
+    ats, pred, test, tp = _inputs("skewed")
+    tp = tp.clone()
+    n_fused = int(((tp >= 0) & (tp < 7)).sum())
+    assert bool(((tp[WIDE_BAD] >= 0) & (tp[WIDE_BAD] < 7)).all()), (
+        "the rows given out-of-range predictions must be ordinary fused rows")
+    tp[WIDE_BAD] = torch.tensor([-1, 100000])
+    dsa = DSA(ats, pred, device=dev)
+    lsa = MultiModalSA.build_by_class(
+        ats, pred, lambda a, p: LSA(a, max_features=200, device=dev)
+    )
+    fast = FusedPrioritizer(dsa, lsa, dev, pairwise_dtype=torch.bfloat16)
+    assert fast.fast and fast.lsa_ready
+    assert fast.lsa_d > 64
+    test, tp = test.to(dev), tp.to(dev)
+    fast(test, tp)  # allocates the workspaces
+    torch.cuda.synchronize()
+    ws = fast._ws[tuple(test.shape)]
+    ws["white"].view(torch.int16).fill_(NAN_BITS)
+    ws["wan"].fill_(float("nan"))
+    ws["pkde"].fill_(float("nan"))
+    out = fast(test, tp)
+    torch.cuda.synchronize()
+    return {"fast_obj": fast, "ws": ws, "test": test, "tp": tp, "out": out,
+            "n_fused": n_fused - len(WIDE_BAD)}
+
+
+def test_wide_lsa_stage_oracles():
+    """Each LSA stage of a d > 64 call against its float64 oracle
+    (tests/test_gpu_lsa_oracles.py), fed the call's own workspaces."""
+    from test_gpu_lsa_oracles import (
+        NAN_BITS, lsa_score_check, rownorm_check, whiten_check,
+    )
+
+    r = _run_wide()
+    fast, ws = r["fast_obj"], r["ws"]
+    worst_w = whiten_check(
+        r["test"].to(torch.bfloat16), ws["rowmap"], ws["tseg"], fast.lsa_nseg,
+        fast.lsa_keep, fast.lsa_wt, ws["white"], prefill_bits=NAN_BITS,
+    )
+    tseg, wseg = ws["tseg"].tolist(), fast.lsa_nseg.tolist()
+    worst_n = 0.0
+    # `wan` rows of non-fused classes come from the NaN-prefilled `white` rows
+    # the whiten kernel skips and are never read: there is no value to judge
+    for c in range(fast.num_classes):
+        lo, hi = tseg[c], tseg[c + 1]
+        if hi > lo and wseg[c + 1] > wseg[c]:
+            worst_n = max(worst_n,
+                          rownorm_check(ws["white"][lo:hi], ws["wan"][lo:hi]))
+    assert bool(torch.isnan(ws["wan"][tseg[-1]:]).all())
+    worst_k = lsa_score_check(
+        ws["white"], ws["wan"], fast.lsa_wtrainS16, fast.lsa_wnormS16,
+        ws["tseg"], fast.lsa_nseg, ws["rowmap"], fast.lsa_cls_fused,
+        fast.lsa_cls_const, r["out"][1], float("inf"),
+    )
+    print(f"[wide d={fast.lsa_d}] worst ratio: whiten {worst_w:.4f} "
+          f"rownorm {worst_n:.4f} score {worst_k:.4f}")
+    # the const / unseen / out-of-range rows the score oracle pinned exactly
+    tp, lsa = r["tp"], r["out"][1]
+    assert bool((lsa[tp == SINGLETON] == 0.0).all())
+    assert bool((lsa[tp == UNSEEN] == float("inf")).all())
+    assert bool((lsa[WIDE_BAD] == float("inf")).all())
+    fused = (tp >= 0) & (tp < 7)
+    assert int(fused.sum()) == r["n_fused"]
+    assert int(fused.sum()) + int((tp == SINGLETON).sum()) + int(
+        (tp == UNSEEN).sum()) + len(WIDE_BAD) == tp.numel()
+    assert bool(torch.isfinite(lsa[fused]).all())
+
+
 def test_const_and_unseen_classes_exact():
     r = _run("skewed")
     dsa, lsa = r["fast"]
