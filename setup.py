@@ -30,6 +30,7 @@ setup(
                 os.path.join(HIP_DIR, "coverage_suite.hip"),
                 os.path.join(HIP_DIR, "cam.hip"),
                 os.path.join(HIP_DIR, "cam_many.hip"),
+                os.path.join(HIP_DIR, "kmeans_many.hip"),
                 os.path.join(HIP_DIR, "resnet_fused.hip"),
                 os.path.join(HIP_DIR, "resnet_stages.hip"),
                 os.path.join(HIP_DIR, "scores.hip"),

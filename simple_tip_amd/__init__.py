@@ -16,3 +16,22 @@ for AMD Instinct MI355X (gfx950):
 """
 
 __version__ = "0.1.0"
+
+#: public names resolved on first use, so that importing the package stays
+#: free of torch
+_LAZY = {
+    "kmeans_fit_many": "simple_tip_amd.core.kmeans",
+    "silhouette_scores_many": "simple_tip_amd.core.kmeans",
+    "KMEANS_MODES": "simple_tip_amd.core.surprise",
+    "resolve_kmeans_mode": "simple_tip_amd.core.surprise",
+}
+
+__all__ = sorted(_LAZY)
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+
+        return getattr(importlib.import_module(_LAZY[name]), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

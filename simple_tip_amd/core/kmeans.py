@@ -4,10 +4,16 @@ Replaces sklearn's KMeans/silhouette_score used by the reference's
 ``_KmeansDiscriminator`` (src/core/surprise.py:102-133). Both the Lloyd
 assignment step and the silhouette score are pairwise-distance problems, so
 on MI355X they run on the same MFMA pairwise-sqdist kernel as DSA/KDE
-(ops.pairwise_sqdist / ops.rowmin_l2). Deterministic for a given seed.
+(ops.pairwise_sqdist / ops.rowmin_l2).
+
+Determinism: on CPU every function here is deterministic for a given seed,
+and so is the batched path (``kmeans_fit_many`` / ``silhouette_scores_many``)
+on the GPU, whose sums have a fixed order. ``kmeans_fit`` on the GPU updates
+its centres with ``index_add_``, i.e. float atomic adds, so its centres can
+differ from run to run in the last bits.
 """
 
-from typing import Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
@@ -105,3 +111,111 @@ def silhouette_score(x: torch.Tensor, labels: torch.Tensor, chunk: int = 2048) -
         s = torch.where(own_counts > 1, s, torch.zeros_like(s))
         s_vals[s0 : s0 + chunk] = s
     return float(s_vals.mean())
+
+
+#: Lloyd iterations between two read-backs of the problems still moving
+_ACTIVE_POLL = 8
+
+
+def kmeans_fit_many(
+    x: torch.Tensor,
+    ks: Sequence[int],
+    n_init: int = 10,
+    max_iter: int = 300,
+    seed: int = 0,
+    tol: float = 1e-4,
+    stats: dict = None,
+) -> Dict[int, Tuple[torch.Tensor, torch.Tensor, float]]:
+    """``{k: (centers, labels, inertia)}``, each what
+    ``kmeans_fit(x, k, n_init, max_iter, seed, tol)`` returns.
+
+    For each k the ``n_init`` k-means++ seeds are drawn up front from a
+    fresh generator (the stream ``kmeans_fit`` sees: Lloyd never touches
+    it); then all ``len(ks) * n_init`` problems iterate in lockstep through
+    ``ops.lloyd_assign_many`` / ``ops.lloyd_update_many``. The set of
+    problems still moving is read back every ``_ACTIVE_POLL`` iterations
+    only; a converged problem is left untouched by further updates, so the
+    late read changes no result. On CPU the results equal ``kmeans_fit``'s
+    exactly; on the GPU they are reproducible from run to run. ``stats``
+    (optional dict) receives ``lloyd_iterations``, the updates run.
+    """
+    ks = [int(k) for k in ks]
+    x = x.float().contiguous()
+    inits = []
+    for k in ks:
+        gen = torch.Generator().manual_seed(seed)
+        inits += [_kmeanspp_init(x, k, gen) for _ in range(n_init)]
+    seg_host = [0]
+    for c in inits:
+        seg_host.append(seg_host[-1] + c.shape[0])
+    centers = torch.cat(inits, dim=0).contiguous()
+    seg = torch.tensor(seg_host, dtype=torch.int32, device=x.device)
+    active = torch.ones(len(inits), dtype=torch.int32, device=x.device)
+    xnorm = ops.row_sqnorms(x)
+    # on the host the read is free, and an early stop saves whole assigns
+    poll = _ACTIVE_POLL if x.is_cuda else 1
+    iters = 0
+    while iters < max_iter:
+        labels, _ = ops.lloyd_assign_many(x, centers, seg, seg_host, xnorm)
+        ops.lloyd_update_many(x, labels, centers, seg, active, tol, seg_host)
+        iters += 1
+        if iters % poll == 0 and not bool(active.any()):
+            break
+    if stats is not None:
+        stats["lloyd_iterations"] = iters
+    labels, mind = ops.lloyd_assign_many(x, centers, seg, seg_host, xnorm)
+    # per problem the expression of kmeans_fit; one read-back for all
+    inertias = torch.stack(
+        [(mind[p] * mind[p]).sum() for p in range(len(inits))]
+    ).tolist()
+    out = {}
+    for i, k in enumerate(ks):
+        best = None
+        for p in range(i * n_init, (i + 1) * n_init):
+            if best is None or inertias[p] < inertias[best]:
+                best = p
+        out[k] = (
+            centers[seg_host[best] : seg_host[best + 1]].clone(),
+            labels[best].long(),
+            inertias[best],
+        )
+    return out
+
+
+def silhouette_scores_many(
+    x: torch.Tensor, labels_list: Sequence[torch.Tensor]
+) -> List[float]:
+    """``[silhouette_score(x, labels) for labels in labels_list]`` from one
+    ``ops.silhouette_cluster_sums`` call: the distances are computed once for
+    all labelings, the per-row arithmetic of :func:`silhouette_score` is then
+    applied to the [N, C] cluster sums."""
+    x = x.float().contiguous()
+    n = x.shape[0]
+    lab = torch.stack([l.to(x.device).long() for l in labels_list])  # [P, N]
+    ks = (lab.max(dim=1).values + 1).tolist()
+    seg_host = [0]
+    for k in ks:
+        seg_host.append(seg_host[-1] + int(k))
+    seg = torch.tensor(seg_host, dtype=torch.int32, device=x.device)
+    sums_all = ops.silhouette_cluster_sums(
+        x, lab.to(torch.int32).contiguous(), seg, seg_host
+    )
+    rows = torch.arange(n, device=x.device)
+    means = []
+    for p, k in enumerate(ks):
+        own = lab[p]
+        sums = sums_all[:, seg_host[p] : seg_host[p + 1]]
+        onehot = torch.zeros(n, int(k), dtype=x.dtype, device=x.device)
+        onehot[rows, own] = 1.0
+        counts = onehot.sum(dim=0)
+        own_counts = counts[own]
+        a = sums[rows, own] / (own_counts - 1).clamp_min(1.0)
+        mean_to = sums / counts.clamp_min(1.0)
+        # as silhouette_score: empty clusters and the own one leave the min
+        mean_to = mean_to.masked_fill((counts == 0).unsqueeze(0), float("inf"))
+        mean_to[rows, own] = float("inf")
+        b = mean_to.min(dim=1).values
+        s = (b - a) / torch.maximum(a, b)
+        s = torch.where(own_counts > 1, s, torch.zeros_like(s))
+        means.append(s.mean())
+    return [float(v) for v in torch.stack(means).tolist()]

@@ -21,7 +21,13 @@ import torch
 from .. import ops
 from .bitmap import BitProfile
 from .kde import StableGaussianKDE
-from .kmeans import kmeans_fit, kmeans_predict, silhouette_score
+from .kmeans import (
+    kmeans_fit,
+    kmeans_fit_many,
+    kmeans_predict,
+    silhouette_score,
+    silhouette_scores_many,
+)
 
 Activations = Union[List, np.ndarray, torch.Tensor]
 Predictions = Union[List, np.ndarray, torch.Tensor]
@@ -158,11 +164,32 @@ def _by_class_discriminator(activations, predictions):
     return _class_predictions(predictions)
 
 
+KMEANS_MODES = ("looped", "batched")
+
+
+def resolve_kmeans_mode(kmeans_mode: str) -> str:
+    """The k-means discovery mode in force: ``TIP_KMEANS_MODE`` overrides the
+    argument; anything but ``"looped"`` or ``"batched"`` raises ValueError."""
+    kmeans_mode = os.environ.get("TIP_KMEANS_MODE", kmeans_mode)
+    if kmeans_mode not in KMEANS_MODES:
+        raise ValueError(
+            f"kmeans_mode must be 'looped' or 'batched', got {kmeans_mode!r}"
+        )
+    return kmeans_mode
+
+
 class _KmeansDiscriminator:
     """Chooses k in potential_k by silhouette on (subsampled) training data
     and assigns new samples to the nearest center
     (reference surprise.py:102-133; sklearn replaced by the device-capable
-    core.kmeans Lloyd/silhouette built on the pairwise kernel)."""
+    core.kmeans Lloyd/silhouette built on the pairwise kernel).
+
+    ``kmeans_mode="looped"`` (the default) fits and scores one k after the
+    other. ``"batched"`` runs every restart of every k in lockstep
+    (``kmeans_fit_many``) and scores all k from one pass over the distances
+    (``silhouette_scores_many``); the selection rule is the same: k
+    ascending, a strictly greater silhouette wins. ``TIP_KMEANS_MODE``
+    overrides the argument."""
 
     def __init__(
         self,
@@ -172,12 +199,26 @@ class _KmeansDiscriminator:
         subsampling_seed: int = 0,
         n_init: int = 10,
         max_iter: int = 300,
+        kmeans_mode: str = "looped",
     ):
+        self.kmeans_mode = resolve_kmeans_mode(kmeans_mode)
         data = _flatten_layers(training_data).float()
         data = _subsample_array(subsampling, data, seed=subsampling_seed)
         self.best_score = -float("inf")
         self.best_k = None
         self.best_centers = None
+        if self.kmeans_mode == "batched":
+            ks = list(potential_k)
+            fits = kmeans_fit_many(
+                data, ks, n_init=n_init, max_iter=max_iter, seed=subsampling_seed
+            )
+            scores = silhouette_scores_many(data, [fits[k][1] for k in ks])
+            for k, score in zip(ks, scores):
+                if score > self.best_score:
+                    self.best_score = score
+                    self.best_k = k
+                    self.best_centers = fits[k][0]
+            return
         for k in potential_k:
             centers, labels, _ = kmeans_fit(
                 data, k, n_init=n_init, max_iter=max_iter, seed=subsampling_seed
@@ -217,6 +258,7 @@ class MultiModalSA(SA):
         max_iter: int = 300,
         subsampling: Union[int, float] = 1.0,
         subsampling_seed: int = 0,
+        kmeans_mode: str = "looped",
     ) -> "MultiModalSA":
         disc = _KmeansDiscriminator(
             training_data=activations,
@@ -225,6 +267,7 @@ class MultiModalSA(SA):
             max_iter=max_iter,
             subsampling=subsampling,
             subsampling_seed=subsampling_seed,
+            kmeans_mode=kmeans_mode,
         )
         return MultiModalSA.build(activations, predictions, disc, sa_constructor)
 

@@ -15,7 +15,15 @@ import torch
 
 from ..config import NUM_SC_BUCKETS
 from ..core.prioritizers import cam, cam_many
-from ..core.surprise import DSA, LSA, MDSA, MLSA, MultiModalSA, SurpriseCoverageMapper
+from ..core.surprise import (
+    DSA,
+    LSA,
+    MDSA,
+    MLSA,
+    MultiModalSA,
+    SurpriseCoverageMapper,
+    resolve_kmeans_mode,
+)
 from ..core.timer import DeviceTimer
 from .model_handler import BaseModel
 
@@ -32,8 +40,8 @@ class SurpriseHandler:
         "pc-mlsa": lambda x, y: MultiModalSA.build_by_class(
             x, y, lambda a, p: MLSA(a, num_components=3)
         ),
-        "pc-mmdsa": lambda x, y: MultiModalSA.build_with_kmeans(
-            x, y, lambda a, p: MDSA(a), potential_k=range(2, 6), subsampling=0.3
+        "pc-mmdsa": lambda x, y, **kw: MultiModalSA.build_with_kmeans(
+            x, y, lambda a, p: MDSA(a), potential_k=range(2, 6), subsampling=0.3, **kw
         ),
     }
 
@@ -50,8 +58,15 @@ class SurpriseHandler:
         dist_shard: bool = False,
         modal_sa_mode: str = "per_mode",
         cam_mode: str = "per_metric",
+        kmeans_mode: str = "looped",
     ):
         from ..parallel.dist import get_world_size
+
+        # "batched": pc-mmdsa's k-means discovery runs every restart of every
+        # k in lockstep and scores all k from one pass over the distances
+        # (core.kmeans.kmeans_fit_many / silhouette_scores_many); "looped"
+        # (the default) fits one k after the other. TIP_KMEANS_MODE overrides.
+        self.kmeans_mode = resolve_kmeans_mode(kmeans_mode)
 
         # "fused": the three Gaussian configurations (pc-mdsa, pc-mlsa,
         # pc-mmdsa) are fit as usual and then MultiModalSA.fuse()d, so every
@@ -137,7 +152,12 @@ class SurpriseHandler:
             setup_timer = DeviceTimer()
             with setup_timer:
                 logger.info("Creating %s instance", sa_name)
-                sa = sa_func(self.train_ats, self.train_pred)
+                if sa_name == "pc-mmdsa" and self.kmeans_mode != "looped":
+                    sa = sa_func(
+                        self.train_ats, self.train_pred, kmeans_mode=self.kmeans_mode
+                    )
+                else:
+                    sa = sa_func(self.train_ats, self.train_pred)
                 if isinstance(sa, DSA) and dsa_badge_size is not None:
                     sa.badge_size = dsa_badge_size
                 if self.modal_sa_mode == "fused" and sa_name in self.FUSABLE_SA:

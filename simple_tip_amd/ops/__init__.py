@@ -175,6 +175,101 @@ def grouped_gaussian_scores(
     return _route(x).grouped_gaussian_scores(x, group, comp_off, means, mats, logc)
 
 
+# --- batched k-means ---------------------------------------------------------
+#
+# P problems share the rows ``x`` [N, D] (float32, contiguous). Their centres
+# are stacked in ``centers`` [C, D]; ``seg`` (int32 [P+1], starting at 0,
+# strictly ascending) gives problem p the rows ``seg[p] .. seg[p+1]`` of it.
+# ``seg_host`` is an optional host copy of ``seg`` (a sequence of ints) that
+# saves the validation from reading a device ``seg`` back.
+#
+# GPU envelope of the three ops: P <= 64 problems, at most 16 centres per
+# problem, C <= 256. Outside it, and for a non-contiguous or non-float32
+# ``x``, a ``seg`` that does not ascend or tensors on different devices, the
+# calls raise ValueError; they never fall back.
+
+
+def lloyd_assign_many(
+    x: torch.Tensor,
+    centers: torch.Tensor,
+    seg: torch.Tensor,
+    seg_host: Sequence[int] = None,
+    xnorm: torch.Tensor = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(labels int32 [P, N], mind float32 [P, N])``: for every problem the
+    problem-local index of the nearest centre of each row and its L2
+    distance, ties to the lowest index.
+
+    ``labels[p]`` and ``mind[p]`` equal
+    ``rowmin_l2(x, centers[seg[p]:seg[p+1]])`` bit for bit. On GPU tensors
+    one exact-fp32 launch of the pairwise tile core computes the distances to
+    all C centres and a small kernel takes the per-problem minima; ``xnorm``
+    (GPU only) passes the squared row norms of ``x`` from
+    :func:`row_sqnorms`, which a loop over the same ``x`` computes once.
+    """
+    impl = _route(x)
+    if impl is fallback:
+        return fallback.lloyd_assign_many(x, centers, seg, seg_host)
+    return impl.lloyd_assign_many(x, centers, seg, seg_host, xnorm)
+
+
+def row_sqnorms(x: torch.Tensor) -> torch.Tensor:
+    """Squared row norms of a GPU ``x`` as the pairwise kernels compute them
+    (the ``xnorm`` of :func:`lloyd_assign_many`); ``None`` for CPU tensors,
+    whose implementation takes none."""
+    impl = _route(x)
+    return None if impl is fallback else impl.row_sqnorms(x)
+
+
+def lloyd_update_many(
+    x: torch.Tensor,
+    labels: torch.Tensor,
+    centers: torch.Tensor,
+    seg: torch.Tensor,
+    active: torch.Tensor,
+    tol: float = 1e-4,
+    seg_host: Sequence[int] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One Lloyd update of every problem with ``active[p] != 0`` (int32 [P]);
+    returns ``(shift float32 [P], counts int32 [C])``.
+
+    Every centre of an active problem is replaced IN PLACE by the mean of the
+    rows that ``labels[p]`` gives it; a centre without rows keeps its value
+    and labels outside the problem's range are ignored. ``shift[p]`` is the
+    summed squared movement of the problem's centres and ``active[p]`` is
+    cleared, on the device, when ``shift[p] <= tol``. Inactive problems are
+    left untouched; their ``shift`` and ``counts`` are 0.
+
+    On CPU the arithmetic is ``kmeans_fit``'s own. On GPU tensors one pass
+    over ``x`` serves all problems and every sum has a fixed order (rows
+    ascending within 256-row chunks, chunks ascending, no float atomics):
+    two calls give bit-identical centres and a problem's result does not
+    depend on the other problems of the call.
+    """
+    return _route(x).lloyd_update_many(x, labels, centers, seg, active, tol, seg_host)
+
+
+def silhouette_cluster_sums(
+    x: torch.Tensor,
+    labels: torch.Tensor,
+    seg: torch.Tensor,
+    seg_host: Sequence[int] = None,
+) -> torch.Tensor:
+    """float32 [N, C]: ``out[i, seg[p] + c]`` is the sum of ``||x_i - x_j||``
+    over the rows ``j != i`` with ``labels[p, j] == c`` (``labels`` int32
+    [P, N]; a label outside its problem's range belongs to no cluster). The
+    ``j == i`` term is exactly 0.
+
+    On GPU tensors the N x N distance matrix is never written: an epilogue of
+    the pairwise tile core adds each tile's distances into per-row cluster
+    bins, for every labeling of a pass at once, and a fold adds the
+    column-strip partials in ascending order. One Gram pass serves
+    consecutive problems of up to 16 bins in total (k = 2..5 is one pass);
+    further problems take further passes.
+    """
+    return _route(x).silhouette_cluster_sums(x, labels, seg, seg_host)
+
+
 # --- score / profile ops ----------------------------------------------------
 
 def softmax_uncertainties(probs: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -911,3 +911,141 @@ def grouped_gaussian_scores(
         out[torch.isneginf(out)] = float("inf")  # unplaced / empty group
         return out
     return -torch.logsumexp(t, dim=1)
+
+
+# ---------------------------------------------------------------------------
+# Batched k-means: P problems over the same rows, centres stacked
+# ---------------------------------------------------------------------------
+
+
+def kmeans_many_segments(seg, seg_host=None) -> List[int]:
+    """The host list of ``seg`` (int32 [P+1], problem p owns stacked centres
+    ``seg[p] .. seg[p+1]``), validated: starts at 0 and strictly ascending.
+    ``seg_host`` is the caller's own host copy, which saves reading a device
+    ``seg`` back."""
+    if not isinstance(seg, torch.Tensor) or seg.dtype != torch.int32 or seg.dim() != 1:
+        raise ValueError("seg must be an int32 [P+1] tensor")
+    s = [int(v) for v in (seg.cpu().tolist() if seg_host is None else seg_host)]
+    if len(s) != seg.shape[0] or len(s) < 2:
+        raise ValueError("seg must hold P+1 >= 2 offsets")
+    if s[0] != 0 or any(b <= a for a, b in zip(s, s[1:])):
+        raise ValueError(f"seg must start at 0 and ascend strictly (got {s})")
+    return s
+
+
+def _kmeans_many_check(x, seg_list, labels=None, centers=None, active=None):
+    """Argument checks shared by the CPU and the GPU implementations."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous float32 [N, D] tensor")
+    n, d = x.shape
+    p, c = len(seg_list) - 1, seg_list[-1]
+    if n < 1 or d < 1:
+        raise ValueError("x must have at least one row and one column")
+    if centers is not None:
+        if (
+            centers.dim() != 2
+            or centers.dtype != torch.float32
+            or not centers.is_contiguous()
+            or tuple(centers.shape) != (c, d)
+        ):
+            raise ValueError(
+                f"centers must be a contiguous float32 [{c}, {d}] tensor "
+                f"(got {centers.dtype}, shape {tuple(centers.shape)})"
+            )
+    if labels is not None:
+        if (
+            labels.dtype != torch.int32
+            or not labels.is_contiguous()
+            or tuple(labels.shape) != (p, n)
+        ):
+            raise ValueError(f"labels must be a contiguous int32 [{p}, {n}] tensor")
+    if active is not None:
+        if (
+            active.dtype != torch.int32
+            or not active.is_contiguous()
+            or tuple(active.shape) != (p,)
+        ):
+            raise ValueError(f"active must be a contiguous int32 [{p}] tensor")
+    return n, d, p, c
+
+
+def _same_device(x, **others):
+    for name, t in others.items():
+        if t is not None and t.device != x.device:
+            raise ValueError(
+                f"{name} is on {t.device}, x on {x.device}; all tensors "
+                "must share one device"
+            )
+
+
+def lloyd_assign_many(x, centers, seg, seg_host=None):
+    """Nearest centre per row and problem: ``rowmin_l2`` per segment."""
+    s = kmeans_many_segments(seg, seg_host)
+    _same_device(x, centers=centers, seg=seg)
+    n, _, p, _ = _kmeans_many_check(x, s, centers=centers)
+    labels = torch.empty(p, n, dtype=torch.int32, device=x.device)
+    mind = torch.empty(p, n, dtype=torch.float32, device=x.device)
+    for q in range(p):
+        d, idx = rowmin_l2(x, centers[s[q] : s[q + 1]])
+        labels[q] = idx.to(torch.int32)
+        mind[q] = d
+    return labels, mind
+
+
+def lloyd_update_many(x, labels, centers, seg, active, tol=1e-4, seg_host=None):
+    """One Lloyd update per active problem with ``kmeans_fit``'s own
+    arithmetic (``index_add_`` sums, the same ``shift`` expression)."""
+    s = kmeans_many_segments(seg, seg_host)
+    _same_device(x, labels=labels, centers=centers, seg=seg, active=active)
+    _, _, p, c = _kmeans_many_check(x, s, labels=labels, centers=centers, active=active)
+    shift = torch.zeros(p, dtype=torch.float32, device=x.device)
+    counts_all = torch.zeros(c, dtype=torch.int32, device=x.device)
+    act = active.tolist()
+    for q in range(p):
+        if not act[q]:
+            continue
+        old = centers[s[q] : s[q + 1]]
+        k = old.shape[0]
+        lab = labels[q].long()
+        rows = x
+        valid = (lab >= 0) & (lab < k)
+        if not bool(valid.all()):
+            lab, rows = lab[valid], x[valid]
+        new_centers = torch.zeros_like(old)
+        counts = torch.zeros(k, dtype=x.dtype, device=x.device)
+        new_centers.index_add_(0, lab, rows)
+        counts.index_add_(0, lab, torch.ones(lab.shape[0], dtype=x.dtype, device=x.device))
+        counts_all[s[q] : s[q + 1]] = counts.to(torch.int32)
+        empty = counts == 0
+        counts = counts.clamp_min(1.0)
+        new_centers /= counts.unsqueeze(1)
+        new_centers[empty] = old[empty]
+        sh = (new_centers - old).pow(2).sum()
+        centers[s[q] : s[q + 1]] = new_centers
+        shift[q] = sh
+        if float(sh) <= tol:
+            active[q] = 0
+    return shift, counts_all
+
+
+def silhouette_cluster_sums(x, labels, seg, seg_host=None, chunk: int = 2048):
+    """``out[i, seg[p]+c]``: sum of the L2 distances from row i to the other
+    rows that labeling p puts into cluster c. Labels outside a problem's
+    range belong to no cluster."""
+    s = kmeans_many_segments(seg, seg_host)
+    _same_device(x, labels=labels, seg=seg)
+    n, _, p, c = _kmeans_many_check(x, s, labels=labels)
+    onehot = torch.zeros(n, c, dtype=x.dtype, device=x.device)
+    rows = torch.arange(n, device=x.device)
+    for q in range(p):
+        lab = labels[q].long()
+        valid = (lab >= 0) & (lab < s[q + 1] - s[q])
+        onehot[rows[valid], s[q] + lab[valid]] = 1.0
+    out = torch.empty(n, c, dtype=x.dtype, device=x.device)
+    for s0 in range(0, n, chunk):
+        xc = x[s0 : s0 + chunk]
+        d = pairwise_sqdist(xc, x).clamp_min_(0).sqrt_()
+        m = xc.shape[0]
+        d[torch.arange(m, device=x.device), torch.arange(s0, s0 + m, device=x.device)] = 0.0
+        out[s0 : s0 + chunk] = d @ onehot
+    return out

@@ -15,6 +15,7 @@
 
 #include "cam_many.h"
 #include "coverage_suite.h"
+#include "kmeans_many.h"
 
 // launchers defined in the .hip translation units
 void launch_rownorm(const float*, int, int, float*, hipStream_t);
@@ -1219,6 +1220,121 @@ std::vector<torch::Tensor> coverage_suite(
 
 int64_t coverage_suite_chunk_py() { return coverage_suite_chunk(); }
 
+// ---- batched k-means (kmeans_many.hip, silhouette epilogue of pairwise.hip).
+// Shapes and the envelope are validated by ops/hip_ops.py; the checks here
+// only keep a wrong call from reaching a kernel.
+
+void check_i32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dtype() == torch::kInt32 && t.is_contiguous(),
+              name, " must be a contiguous int32 GPU tensor");
+}
+
+void check_kmeans_many(const torch::Tensor& x, const torch::Tensor& seg,
+                       int64_t c) {
+  check_f32_2d(x, "x");
+  check_i32(seg, "seg");
+  const int64_t p = seg.numel() - 1;
+  TORCH_CHECK(p >= 1 && p <= KMEANS_MANY_MAX_PROBLEMS, "1..",
+              KMEANS_MANY_MAX_PROBLEMS, " problems");
+  TORCH_CHECK(c >= 1 && c <= KMEANS_MANY_MAX_CENTERS, "1..",
+              KMEANS_MANY_MAX_CENTERS, " centres");
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) < (1 << 24) && x.size(1) >= 1,
+              "x must have 1 .. 2^24 - 1 rows");
+}
+
+std::vector<torch::Tensor> lloyd_assign_many(
+    torch::Tensor x, torch::Tensor centers, torch::Tensor seg,
+    c10::optional<torch::Tensor> xnorm) {
+  check_f32_2d(centers, "centers");
+  check_kmeans_many(x, seg, centers.size(0));
+  TORCH_CHECK(x.size(1) == centers.size(1), "feature dims differ");
+  const int n = x.size(0), c = centers.size(0), d = x.size(1);
+  const int p = seg.numel() - 1;
+  auto xn = xnorm.has_value() ? xnorm.value() : rownorm(x);
+  TORCH_CHECK(xn.is_cuda() && xn.dtype() == torch::kFloat32 &&
+              xn.is_contiguous() && xn.numel() == n, "xnorm must be fp32 [N]");
+  auto cn = rownorm(centers);
+  auto d2 = torch::empty({n, c}, x.options());
+  auto labels = torch::empty({p, n}, x.options().dtype(torch::kInt32));
+  auto mind = torch::empty({p, n}, x.options());
+  launch_pairwise_full(x.data_ptr<float>(), centers.data_ptr<float>(),
+                       xn.data_ptr<float>(), cn.data_ptr<float>(), n, c, d,
+                       d2.data_ptr<float>(), cur_stream());
+  launch_lloyd_argmin(d2.data_ptr<float>(), seg.data_ptr<int>(), n, c, p,
+                      labels.data_ptr<int>(), mind.data_ptr<float>(),
+                      cur_stream());
+  return {labels, mind};
+}
+
+std::vector<torch::Tensor> lloyd_update_many(
+    torch::Tensor x, torch::Tensor labels, torch::Tensor centers,
+    torch::Tensor seg, torch::Tensor active, double tol) {
+  check_f32_2d(centers, "centers");
+  check_kmeans_many(x, seg, centers.size(0));
+  check_i32(labels, "labels");
+  check_i32(active, "active");
+  const int n = x.size(0), c = centers.size(0), d = x.size(1);
+  const int p = seg.numel() - 1;
+  TORCH_CHECK(x.size(1) == centers.size(1), "feature dims differ");
+  TORCH_CHECK(labels.dim() == 2 && labels.size(0) == p && labels.size(1) == n,
+              "labels must be [P, N]");
+  TORCH_CHECK(active.numel() == p, "active must be [P]");
+  const int chunks = lloyd_chunks(n);
+  auto psum = torch::empty({chunks, c, d}, x.options());
+  auto pshift = torch::zeros({c}, x.options());
+  auto counts = torch::empty({c}, x.options().dtype(torch::kInt32));
+  auto shift = torch::empty({p}, x.options());
+  launch_lloyd_update(x.data_ptr<float>(), labels.data_ptr<int>(),
+                      centers.data_ptr<float>(), seg.data_ptr<int>(),
+                      active.data_ptr<int>(), n, d, p, c, tol,
+                      psum.data_ptr<float>(), pshift.data_ptr<float>(),
+                      counts.data_ptr<int>(), shift.data_ptr<float>(),
+                      cur_stream());
+  return {shift, counts};
+}
+
+// `groups` lists the first problem of every Gram pass plus P at the end and
+// `seg_host` is the host copy of seg; a pass has at most silhouette_bins()
+// bins.
+torch::Tensor silhouette_cluster_sums(torch::Tensor x, torch::Tensor labels,
+                                      torch::Tensor seg,
+                                      std::vector<int64_t> seg_host,
+                                      std::vector<int64_t> groups) {
+  const int64_t p = seg.numel() - 1;
+  TORCH_CHECK((int64_t)seg_host.size() == p + 1, "seg_host must match seg");
+  const int c = (int)seg_host[p];
+  check_kmeans_many(x, seg, c);
+  check_i32(labels, "labels");
+  const int n = x.size(0), d = x.size(1);
+  TORCH_CHECK(labels.dim() == 2 && labels.size(0) == p && labels.size(1) == n,
+              "labels must be [P, N]");
+  TORCH_CHECK(groups.size() >= 2 && groups.front() == 0 && groups.back() == p,
+              "groups must run from 0 to P");
+  auto xn = rownorm(x);
+  auto out = torch::zeros({n, c}, x.options());
+  auto ppart = torch::empty(
+      {silhouette_strips(n), n, silhouette_bins()}, x.options());
+  for (size_t g = 0; g + 1 < groups.size(); ++g) {
+    const int64_t p0 = groups[g], p1 = groups[g + 1];
+    TORCH_CHECK(0 <= p0 && p0 < p1 && p1 <= p, "bad group");
+    const int64_t bin0 = seg_host[p0], nbins = seg_host[p1] - bin0;
+    TORCH_CHECK(bin0 >= 0 && nbins >= 1 && nbins <= silhouette_bins() &&
+                bin0 + nbins <= c, "a pass takes 1..", silhouette_bins(),
+                " bins");
+    launch_silhouette_sums(x.data_ptr<float>(), xn.data_ptr<float>(), n, d,
+                           labels.data_ptr<int>(), seg.data_ptr<int>(),
+                           (int)p0, (int)(p1 - p0), (int)bin0, (int)nbins, c,
+                           ppart.data_ptr<float>(), out.data_ptr<float>(),
+                           cur_stream());
+  }
+  return out;
+}
+
+std::vector<int64_t> kmeans_many_envelope() {
+  return {KMEANS_MANY_MAX_PROBLEMS, KMEANS_MANY_MAX_K, KMEANS_MANY_MAX_CENTERS,
+          KMEANS_MANY_CHUNK_ROWS, silhouette_bins()};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1257,6 +1373,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bucketize", &bucketize);
   m.def("coverage_suite", &coverage_suite);
   m.def("coverage_suite_chunk", &coverage_suite_chunk_py);
+  m.def("lloyd_assign_many", &lloyd_assign_many, py::arg("x"),
+        py::arg("centers"), py::arg("seg"), py::arg("xnorm") = py::none());
+  m.def("lloyd_update_many", &lloyd_update_many);
+  m.def("silhouette_cluster_sums", &silhouette_cluster_sums);
+  m.def("kmeans_many_envelope", &kmeans_many_envelope);
   m.def("cam_greedy", &cam_greedy);
   m.def("cam_greedy_many", &cam_greedy_many);
   m.def("cam_many_force_full", &cam_many_force_full);

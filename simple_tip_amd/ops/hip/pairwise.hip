@@ -28,6 +28,9 @@
 //   tile_epilogue_quad   EPI_QUAD: per-row sum of (tile .* centred row), for
 //                        grouped_quad_kernel (Gaussian quadratic forms); it
 //                        shares the main loop and merge_halves_store
+//   silhouette_sums_kernel  x against itself; its epilogue adds the tile's
+//                        distances into per-row cluster bins instead of
+//                        writing them (batched k-means discovery)
 // pairwise_kernel (flat: XCD swizzle, EPI_FULL) and grouped_pairwise_kernel
 // (class segments) differ only in how a block finds its tile and its bounds,
 // so a grouped result equals the per-class flat result bit for bit, and the
@@ -1046,6 +1049,146 @@ __global__ void grouped_kde_final_kernel(
   out_lsa[src] = -(lse + cls_const[cls]);
 }
 
+// ---------------------------------------------------------------------------
+// Silhouette cluster sums (docs/kernels.md "Batched k-means"). X against
+// itself: the tile at (row0, col0) holds the Gram block, and instead of
+// writing sqrt(max(d^2, 0)) out, the epilogue adds it into the bin of its row
+// that the column's label names, for every labeling of the pass at once. A
+// pass serves problems p0 .. p0 + np - 1, whose bins seg[p0] .. seg[p0 + np]
+// number at most SIL_BINS. A block owns one row block and a strip of
+// SIL_STRIP consecutive column blocks, keeps the bins in LDS over the strip
+// and writes one partial per strip; silhouette_fold_kernel adds the strips
+// in ascending order.
+//
+// Epilogue layout. The accumulators hold a column per lane, the bins want a
+// row per thread, so the tile goes through LDS in two 64-column passes: the
+// two waves that own the pass's columns write their distances to
+// T[128][SIL_TROW] (the dead staging buffer; the odd row stride keeps the
+// row-per-lane reads conflict-free), then thread t scans row t & 127,
+// columns (t >> 7) * 32 .. + 31 of the pass in ascending order, adding T into
+// bins[t >> 7][slot][row]. slot[pl][col] is the pass-local bin of column col
+// under problem p0 + pl, or -1 (column past N, label outside the problem).
+// Every sum has one fixed order: columns ascending within a 32-column
+// quarter, quarters of the low pass before the high pass, column blocks of
+// the strip ascending, then quarter set 0 + quarter set 1, then the strips.
+// The diagonal term is set to 0 exactly where row == column.
+// ---------------------------------------------------------------------------
+
+constexpr int SIL_BINS = 16;   // bins one Gram pass serves
+constexpr int SIL_STRIP = 8;   // column blocks folded in LDS by one block
+constexpr int SIL_TROW = 65;   // floats per row of the transposed pass tile
+
+static_assert(BM * SIL_TROW <= 2 * BK * (BM + LDS_PAD),
+              "the transposed pass tile reuses the staging buffer");
+
+__launch_bounds__(256, 2) __global__ void silhouette_sums_kernel(
+    const float* __restrict__ X,       // [N, K]
+    const float* __restrict__ xnorm,   // [N]
+    int N, int K,
+    const int* __restrict__ labels,    // [P, N]
+    const int* __restrict__ seg,       // [P+1]
+    int p0, int np, int C,
+    float* __restrict__ ppart) {       // [strips, N, SIL_BINS]
+  __shared__ float lds[2 * BK * (BM + LDS_PAD)];
+  __shared__ float bins[2][SIL_BINS][BM];
+  __shared__ signed char slot[SIL_BINS][BN];
+
+  const int t = threadIdx.x;
+  const int lane = lane_id();
+  const int wr = wave_id() >> 1;
+  const int wc = wave_id() & 1;
+  const int strip = blockIdx.x;
+  const int row0 = blockIdx.y * BM;
+  const int jb = (N + BN - 1) / BN;
+  const int bj_end = min(jb, (strip + 1) * SIL_STRIP);
+  const int bin0 = seg[p0];
+  const int r = t & (BM - 1);
+  const int q = t >> 7;
+
+  for (int e = t; e < 2 * SIL_BINS * BM; e += blockDim.x)
+    (&bins[0][0][0])[e] = 0.f;
+
+  for (int bj = strip * SIL_STRIP; bj < bj_end; ++bj) {
+    const int col0 = bj * BN;
+    // the previous column block's scans ended in a barrier: slot is free
+    for (int e = t; e < np * BN; e += blockDim.x) {
+      const int pl = e / BN, c = e % BN;
+      const int col = col0 + c;
+      int s = -1;
+      if (col < N) {
+        const int b = seg[p0 + pl];
+        const int k = seg[p0 + pl + 1] - b;
+        const int lab = labels[(int64_t)(p0 + pl) * N + col];
+        if (lab >= 0 && lab < k) s = b - bin0 + lab;
+        if (s >= SIL_BINS || b + lab >= C) s = -1;
+      }
+      slot[pl][c] = (signed char)s;
+    }
+    // the main loop's barriers publish bins (first block) and slot
+    const TileAcc acc = tile_mainloop_f32(X, N, X, N, K, row0, col0, lds,
+                                          lds + BK * (BM + LDS_PAD));
+    const int jl0 = col0 + wc * 64 + (lane & 31);
+    const float bn0 = (jl0 < N) ? xnorm[jl0] : 0.f;
+    const float bn1 = (jl0 + 32 < N) ? xnorm[jl0 + 32] : 0.f;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      if (wc == h) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+#pragma unroll
+          for (int reg = 0; reg < 16; ++reg) {
+            const int row_local = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+            const int block_row = wr * 64 + m * 32 + row_local;
+            const int i = row0 + block_row;
+            const float an = (i < N) ? xnorm[i] : 0.f;
+            float d0 = sqrtf(fmaxf(an + bn0 - 2.f * acc.t[m][0][reg], 0.f));
+            float d1 = sqrtf(fmaxf(an + bn1 - 2.f * acc.t[m][1][reg], 0.f));
+            if (i == jl0) d0 = 0.f;
+            if (i == jl0 + 32) d1 = 0.f;
+            lds[block_row * SIL_TROW + (lane & 31)] = d0;
+            lds[block_row * SIL_TROW + 32 + (lane & 31)] = d1;
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int jj = 0; jj < 32; ++jj) {
+        const int cl = q * 32 + jj;
+        const float d = lds[r * SIL_TROW + cl];
+#pragma unroll 1
+        for (int pl = 0; pl < np; ++pl) {
+          const int s = slot[pl][h * 64 + cl];  // one address per wave
+          if (s >= 0) bins[q][s][r] += d;
+        }
+      }
+      __syncthreads();  // T, and after the last pass slot, may be rewritten
+    }
+  }
+
+  for (int e = t; e < BM * SIL_BINS; e += blockDim.x) {
+    const int rr = e / SIL_BINS, b = e % SIL_BINS;
+    const int i = row0 + rr;
+    if (i < N)
+      ppart[((int64_t)strip * N + i) * SIL_BINS + b] =
+          bins[0][b][rr] + bins[1][b][rr];
+  }
+}
+
+// out[i, bin0 + b] = sum of the strips' partials of (row i, bin b), strips
+// ascending; one thread per (row, bin of the pass).
+__global__ void silhouette_fold_kernel(
+    const float* __restrict__ ppart, int strips, int N, int bin0, int nbins,
+    int C, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)N * SIL_BINS) return;
+  const int i = (int)(e / SIL_BINS), b = (int)(e % SIL_BINS);
+  if (b >= nbins || bin0 + b >= C) return;
+  float s = 0.f;
+  for (int st = 0; st < strips; ++st)
+    s += ppart[((int64_t)st * N + i) * SIL_BINS + b];
+  out[(int64_t)i * C + bin0 + b] = s;
+}
+
 // Row squared norms: one wave per row.
 __global__ void rownorm_kernel(
     const float* __restrict__ X, int rows, int K, float* __restrict__ out) {
@@ -1119,6 +1262,24 @@ void launch_grouped_kde(const float* a, const float* b, const float* an,
       a, b, an, bn, tseg, nseg, nclasses, bp, k, nullptr, nullptr, pkde);
   grouped_kde_combine_kernel<<<ceil_div(bp, 256), 256, 0, s>>>(
       pkde, tseg, nseg, nclasses, bp, out_lse);
+}
+
+// One silhouette pass: the cluster sums of problems p0 .. p0 + np - 1 (bins
+// bin0 .. bin0 + nbins - 1 of the C columns of `out`, nbins <= SIL_BINS).
+// ppart holds silhouette_strips(n) * n * SIL_BINS floats.
+int silhouette_bins() { return SIL_BINS; }
+int silhouette_strips(int n) { return ceil_div(ceil_div(n, BN), SIL_STRIP); }
+
+void launch_silhouette_sums(const float* x, const float* xnorm, int n, int k,
+                            const int* labels, const int* seg, int p0, int np,
+                            int bin0, int nbins, int c, float* ppart,
+                            float* out, hipStream_t s) {
+  const int strips = silhouette_strips(n);
+  dim3 grid(strips, ceil_div(n, BM));
+  silhouette_sums_kernel<<<grid, 256, 0, s>>>(x, xnorm, n, k, labels, seg, p0,
+                                              np, c, ppart);
+  silhouette_fold_kernel<<<ceil_div((int64_t)n * SIL_BINS, 256), 256, 0, s>>>(
+      ppart, strips, n, bin0, nbins, c, out);
 }
 
 // Dispatch of the bf16 row-min launchers. The pipelined kernel serves K a

@@ -623,3 +623,89 @@ def bucketize_profile(values: torch.Tensor, thresholds: torch.Tensor) -> torch.T
         thresholds.to(values.device).double().contiguous(),
         thresholds.shape[0] - 1,
     )
+
+
+#: device envelope of the batched k-means ops (kmeans_many.hip): problems per
+#: call, centres per problem, stacked centres per call; the rows one block of
+#: the update folds before it writes a partial; the bins one Gram pass of
+#: silhouette_cluster_sums serves
+(
+    KMEANS_MANY_MAX_PROBLEMS,
+    KMEANS_MANY_MAX_K,
+    KMEANS_MANY_MAX_CENTERS,
+    KMEANS_MANY_CHUNK_ROWS,
+    SILHOUETTE_PASS_BINS,
+) = _ext.kmeans_many_envelope()
+
+
+def _kmeans_many_args(x, seg, seg_host, **tensors):
+    """Validate the arguments shared by the three batched k-means ops and
+    return the host segment list."""
+    from . import fallback
+
+    s = fallback.kmeans_many_segments(seg, seg_host)
+    fallback._same_device(x, seg=seg, **tensors)
+    fallback._kmeans_many_check(x, s, **tensors)
+    p, c = len(s) - 1, s[-1]
+    if p > KMEANS_MANY_MAX_PROBLEMS or c > KMEANS_MANY_MAX_CENTERS:
+        raise ValueError(
+            f"batched k-means on GPU takes P <= {KMEANS_MANY_MAX_PROBLEMS} "
+            f"problems and C <= {KMEANS_MANY_MAX_CENTERS} stacked centres "
+            f"(got P={p}, C={c})"
+        )
+    widest = max(b - a for a, b in zip(s, s[1:]))
+    if widest > KMEANS_MANY_MAX_K:
+        raise ValueError(
+            f"batched k-means on GPU takes at most {KMEANS_MANY_MAX_K} "
+            f"centres per problem (got {widest})"
+        )
+    if x.shape[0] >= 1 << 24:
+        raise ValueError("batched k-means on GPU takes fewer than 2^24 rows")
+    if not seg.is_contiguous():
+        raise ValueError("seg must be contiguous")
+    return s
+
+
+def row_sqnorms(x: torch.Tensor) -> torch.Tensor:
+    """Squared row norms as the pairwise kernels compute them."""
+    return _ext.rownorm(x)
+
+
+def lloyd_assign_many(x, centers, seg, seg_host=None, xnorm=None):
+    """One EPI_FULL launch against the stacked centres, then the per-problem
+    arg-min; ``xnorm`` reuses the row norms of ``x`` (:func:`row_sqnorms`)."""
+    _kmeans_many_args(x, seg, seg_host, centers=centers)
+    labels, mind = _ext.lloyd_assign_many(x, centers, seg, xnorm)
+    return labels, mind
+
+
+def lloyd_update_many(x, labels, centers, seg, active, tol=1e-4, seg_host=None):
+    """Fixed-order centre update of the active problems, in place."""
+    _kmeans_many_args(
+        x, seg, seg_host, labels=labels, centers=centers, active=active
+    )
+    shift, counts = _ext.lloyd_update_many(
+        x, labels, centers, seg, active, float(tol)
+    )
+    return shift, counts
+
+
+def silhouette_passes(seg_list: Sequence[int]) -> List[int]:
+    """First problem of every Gram pass of ``silhouette_cluster_sums``, and P
+    at the end: consecutive problems share a pass while their bins number at
+    most ``SILHOUETTE_PASS_BINS``."""
+    groups, bins = [0], 0
+    for p, (a, b) in enumerate(zip(seg_list, seg_list[1:])):
+        if bins + (b - a) > SILHOUETTE_PASS_BINS:
+            groups.append(p)
+            bins = 0
+        bins += b - a
+    groups.append(len(seg_list) - 1)
+    return groups
+
+
+def silhouette_cluster_sums(x, labels, seg, seg_host=None):
+    """[N, C] cluster sums, one Gram pass per group of
+    :func:`silhouette_passes`."""
+    s = _kmeans_many_args(x, seg, seg_host, labels=labels)
+    return _ext.silhouette_cluster_sums(x, labels, seg, s, silhouette_passes(s))
